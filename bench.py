@@ -12,7 +12,9 @@ hash-grid encode -> fused MLP -> K3 composite -> 5*Huber -> K4 -> MLP backward -
 reference's adaptive one (4096 rays initially, re-sized every 16 iterations so that ~2^18 samples are
 marched).  Weak scaling: every rank trains on its own rays, value = rays of all ranks / max-rank time.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, pre-rolls, warms up, times the K steps and prints the headline;
+--full adds every other figure (per-kernel rooflines, frame rendering, CPU baselines, secondary configurations).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -597,6 +599,25 @@ def cpu_baseline(seconds_budget=15.0):
 PREROLL_MIN, PREROLL_MAX = 272, 1024      # past iteration 256: the reference's schedule samples M/4 + M/4 grid cells from there on
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, tr, out):
+    """--dump-outputs: what the last timed step hands its caller (its loss and PSNR, the colours it rendered for its batch) and the
+    parameters it leaves behind (hash table, density and colour MLPs), whole, as float32 DIR/<name>.npy -- 49 MB in all"""
+    mlp = tr.net.mlp
+    psnr = out['log_vars']['psnr']
+    arrays = {'loss': out['loss'], 'psnr': psnr.tensor() if hasattr(psnr, 'tensor') else psnr, 'rgb': tr.net._last['rgb'],
+              'hash_table': mlp.embedder_pos.params, 'density_mlp': mlp.density_net.params, 'color_mlp': mlp.color_net.params}
+    arrays = {k: np.atleast_1d(np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), a)
+
+
 def _respawn_under_torchrun(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, RCCL),
     exactly as the driver's `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...` line would."""
@@ -628,6 +649,11 @@ def main():
     ap.add_argument('--no-f16', action='store_true', help='skip the second line in the reference\'s fp16 MLP precision')
     ap.add_argument('--no-strict', action='store_true', help='skip the secondary line with tcnn\'s default 5 + 5 hidden layers')
     ap.add_argument('--no-extra', action='store_true', help='skip value_all_rows, the real-Lego fixture line and the registry frame time')
+    ap.add_argument('--full', action='store_true', help='after the headline, everything else this benchmark measures: per-kernel rooflines, '
+                    'frame rendering, the CPU baselines and the secondary lines (the --no-* options above select among them); without it '
+                    'a run times the headline steps and prints their line only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed (its loss, PSNR and '
+                    'rendered colours, the parameters it left) to DIR/<name>.npy, float32')
     ap.add_argument('--headline-only', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--cpu-worker', type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument('--cpu-seconds', type=float, default=15.0, help=argparse.SUPPRESS)
@@ -694,19 +720,22 @@ def main():
     align = ((-tr.iter) % freq - first_off) % freq            # un-timed iterations that put the window at that phase
     if align:
         tr.run(align)
-    # which entry point dominates the step?  16 un-timed iterations with events around every training launch (the phase
-    # alignment above is redone afterwards); the timed region then carries events around THAT kernel only
-    ops.TIMER = ops.KernelTimer(only=set(ALGO), train_only=True)
-    for _ in range(freq):
-        tr.step()
-    torch.cuda.synchronize()
-    pre_summ, ops.TIMER = ops.TIMER.summary(), None
-    cand = {k: v[1] for k, v in pre_summ.items() if k != 'xr_rays_sampler'}      # (K1 runs once per refresh window, beside the refresh iteration: not a per-step kernel)
-    dom_pick = max(cand, key=cand.get) if cand else 'xr_hashgrid_bwd'
-    torch.cuda.synchronize()
-    ops.TIMER = ops.KernelTimer(only={dom_pick}, train_only=True)
-    if ops.LIVE_STATS is not None:
-        ops.LIVE_STATS[1:3].zero_()            # running (live rows, valid rows) totals of the backward's row list
+    # the per-kernel figures (roofline) are --full's: a plain run times the steps with nothing around its kernels
+    measure = args.full or args.headline_only
+    if measure:
+        # which entry point dominates the step?  16 un-timed iterations with events around every training launch (the phase
+        # alignment above is redone afterwards); the timed region then carries events around THAT kernel only
+        ops.TIMER = ops.KernelTimer(only=set(ALGO), train_only=True)
+        for _ in range(freq):
+            tr.step()
+        torch.cuda.synchronize()
+        pre_summ, ops.TIMER = ops.TIMER.summary(), None
+        cand = {k: v[1] for k, v in pre_summ.items() if k != 'xr_rays_sampler'}      # (K1 runs once per refresh window, beside the refresh iteration: not a per-step kernel)
+        dom_pick = max(cand, key=cand.get) if cand else 'xr_hashgrid_bwd'
+        torch.cuda.synchronize()
+        ops.TIMER = ops.KernelTimer(only={dom_pick}, train_only=True)
+        if ops.LIVE_STATS is not None:
+            ops.LIVE_STATS[1:3].zero_()            # running (live rows, valid rows) totals of the backward's row list
     rays0, samples0, it0 = tr.rays_done, tr.samples_done, tr.iter
     step_ev = [ops._CEvent() for _ in range(args.steps + 1)]     # one event per iteration boundary
     def exposure_timers():
@@ -718,18 +747,20 @@ def main():
         if tr._loop is not None and tr._loop.exchange is not None:
             out.append(tr._loop.exchange.exposed)
         return out
-    for ex_t in exposure_timers():
+    for ex_t in exposure_timers() if measure else []:
         ex_t.summary()                                           # (drop what earlier iterations recorded)
         ex_t.on = True
     barrier()
     t0 = time.perf_counter()
     # (Trainer.run: the iterations between two grid refreshes are enqueued by one native call each, xr_ngp_loop_run -- the events in
     # front of every iteration and around the dominant entry point are recorded by that call)
-    tr.run(args.steps, iter_events=step_ev)
+    last = tr.run(args.steps, iter_events=step_ev)
     barrier()
     elapsed = time.perf_counter() - t0
     timer, ops.TIMER = ops.TIMER, None
     it1 = tr.iter
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, last)
     # operands the default MLP arithmetic had to saturate at fp16's range, over everything this process has run so far (pre-roll, warm-up,
     # timed window): waves counted by the forward kernels in the range word (xr_set_mlp_range_word); 0 = the fp16 x 2 split was exact
     mlp_range_events = ops.mlp_range_events(dev)
@@ -748,6 +779,61 @@ def main():
         elapsed_max, rays_all, samples_all = float(mx[0]), float(stats[1]), float(stats[2])
     else:
         elapsed_max, rays_all, samples_all = elapsed, float(rays), float(samples)
+
+    def headline_line():
+        """the result line of the timed steps: the headline, its unit and precision, and how the window was set up"""
+        n_refresh = sum(1 for i in range(it0, it1) if i % sampler.update_grid_freq == 0)
+        out = {
+            'metric': 'training rays/s, Instant-NGP Lego (configs/instant_ngp/nerf_blender_local01.py), synthetic 800x800 rays',
+            'value': rays_all / elapsed_max, 'unit': 'rays/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': elapsed_max * 1e3 / args.steps, 'higher_is_better': True,
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'dtype_note': 'f32 tables, parameters, gradients, accumulation, compositor, optimiser state; the fused MLP multiplies on the fp16 '
+                          'matrix cores with every f32 operand split into two fp16 parts (XRNERF_F32_FORWARD=%s: ~4e-7 relative on raw, not '
+                          'f32-exact, operands above 65504 saturated and counted -- mlp_range_events); the reference (tiny-cuda-nn) '
+                          'computes the MLP in plain fp16' % ops.f32_forward(),
+            'library_build': __import__('xrnerf_amd.build', fromlist=['info']).info(),
+            'parity': 'partial: sampling / compositing / grid upkeep pinned to the reference kernels (bit-exact indices and '
+                      'counts, <=1e-4 fp32); hash grid + SH + fused MLP restate tiny-cuda-nn, which is absent from the '
+                      'reference tree (parity unpinned)',
+            'config': {'workload': 'Instant-NGP Lego, hash L=16 F=2 T=2^19, 64-wide fused MLP (1+2 hidden), 800x800, %d images; '
+                                   'full training iterations %d..%d (batch slice + random bg, K1 march, every-16th grid refresh '
+                                   'K6..K11 with its density queries: %d refreshes in the window = round(steps/16), encode, MLP, K3, 5*Huber, K4, '
+                                   'MLP backward, table scatter, %sAdam + L2 + EMA over 12.2 M parameters%s) after %d un-timed '
+                                   'pre-roll + %d warm-up iterations (adaptive batch at its fixed point: %s rays); the '
+                                   'reference\'s dead no-grad MLP pass that only feeds K2\'s dead transmittance loop is skipped; fused-MLP '
+                                   'forward: %s; fused-MLP backward: %s'
+                                   % (args.n_img, it0, it1 - 1, n_refresh, 'gradient all-reduce, ' if world > 1 else '',
+                                      ' (the table\'s update applied inside the scatter: no gradient round trip)' if (world == 1 and tr.fuse_adam) else '',
+                                      preroll, args.warmup + align, hist[-1],
+                                      'fp32 via exact 3-way bf16 operand split on the bf16 MFMA (xr_nerf_mlp_fwd, XR_MLP_BF16X3)' if ops._mlp_mode() == 2
+                                      else 'fp32 results via 2-way fp16 operand split on the fp16 MFMA (xr_nerf_mlp_fwd, XR_MLP_F16X2; 4e-7 relative against float64)'
+                                      if ops._mlp_mode() == 3 else 'fp32 MFMA',
+                                      {'f32': 'fp32 MFMA throughout', 'b2': 'dW on 2-way-split bf16 operands (2^-16 per product), dX chain on the fp32 MFMA',
+                                       'b2x': 'dW and the dX chain on 2-way-split bf16 operands (2^-16 relative per product, fp32 accumulate; '
+                                              '1.0e-5 of max against a float64 statement away from ReLU kinks: profiles/r04_mlp_bwd_denc_outlier.txt), '
+                                              'forward recompute in fp32 (3-way split)',
+                                       'b2f': 'as b2x with the forward recompute on 2-way-split bf16 operands',
+                                       'h2f': 'forward recompute with the forward\'s own arithmetic (2-way fp16 split), dW and the dX chain on 2-way-split '
+                                              'bf16 operands (2^-16 relative per product), fp32 accumulate'}.get(os.environ.get('XR_MLP_BWD_DW', 'h2f'), 'see XR_MLP_BWD_DW')
+                                      if ops._mlp_mode() != 1 else 'fp16 operands, fp32 accumulate'),
+                       'rays_per_step': rays_all / args.steps / world, 'samples_per_ray': samples_all / max(rays_all, 1),
+                       'samples_per_s': samples_all / elapsed_max, 'n_images': args.n_img,
+                       'preroll_iterations': preroll, 'timed_iterations': [it0, it1 - 1], 'grid_refreshes_in_window': n_refresh,
+                       'device_ms_normal_iteration': sum(ms_normal) / max(len(ms_normal), 1),
+                       'device_ms_refresh_iteration': sum(ms_refresh) / max(len(ms_refresh), 1) if ms_refresh else None,
+                       'rays_per_batch_history': hist,
+                       'parallelism': 'ray-sharded data parallel x%d, gradient all-reduce (RCCL)' % world if world > 1 else 'single GPU'},
+            'mlp_range_events': mlp_range_events,
+        }
+        return out
+
+    if not args.full and not args.headline_only:
+        if rank == 0:
+            print(json.dumps(headline_line()))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
     if args.headline_only:
         if rank == 0:
@@ -1006,56 +1092,15 @@ def main():
                 extra['collective']['rccl_log'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:200])}
 
     if rank == 0:
-        n_refresh = sum(1 for i in range(it0, it1) if i % sampler.update_grid_freq == 0)
-        out = {
-            'metric': 'training rays/s, Instant-NGP Lego (configs/instant_ngp/nerf_blender_local01.py), synthetic 800x800 rays',
-            'value': rays_all / elapsed_max, 'unit': 'rays/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': elapsed_max * 1e3 / args.steps, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'dtype_note': 'f32 tables, parameters, gradients, accumulation, compositor, optimiser state; the fused MLP multiplies on the fp16 '
-                          'matrix cores with every f32 operand split into two fp16 parts (XRNERF_F32_FORWARD=%s: ~4e-7 relative on raw, not '
-                          'f32-exact, operands above 65504 saturated and counted -- mlp_range_events); the reference (tiny-cuda-nn) '
-                          'computes the MLP in plain fp16' % ops.f32_forward(),
-            'library_build': __import__('xrnerf_amd.build', fromlist=['info']).info(),
-            'parity': 'partial: sampling / compositing / grid upkeep pinned to the reference kernels (bit-exact indices and '
-                      'counts, <=1e-4 fp32); hash grid + SH + fused MLP restate tiny-cuda-nn, which is absent from the '
-                      'reference tree (parity unpinned)',
-            'config': {'workload': 'Instant-NGP Lego, hash L=16 F=2 T=2^19, 64-wide fused MLP (1+2 hidden), 800x800, %d images; '
-                                   'full training iterations %d..%d (batch slice + random bg, K1 march, every-16th grid refresh '
-                                   'K6..K11 with its density queries: %d refreshes in the window = round(steps/16), encode, MLP, K3, 5*Huber, K4, '
-                                   'MLP backward, table scatter, %sAdam + L2 + EMA over 12.2 M parameters%s) after %d un-timed '
-                                   'pre-roll + %d warm-up iterations (adaptive batch at its fixed point: %s rays); the '
-                                   'reference\'s dead no-grad MLP pass that only feeds K2\'s dead transmittance loop is skipped; fused-MLP '
-                                   'forward: %s; fused-MLP backward: %s'
-                                   % (args.n_img, it0, it1 - 1, n_refresh, 'gradient all-reduce, ' if world > 1 else '',
-                                      ' (the table\'s update applied inside the scatter: no gradient round trip)' if (world == 1 and tr.fuse_adam) else '',
-                                      preroll, args.warmup + align, hist[-1],
-                                      'fp32 via exact 3-way bf16 operand split on the bf16 MFMA (xr_nerf_mlp_fwd, XR_MLP_BF16X3)' if ops._mlp_mode() == 2
-                                      else 'fp32 results via 2-way fp16 operand split on the fp16 MFMA (xr_nerf_mlp_fwd, XR_MLP_F16X2; 4e-7 relative against float64)'
-                                      if ops._mlp_mode() == 3 else 'fp32 MFMA',
-                                      {'f32': 'fp32 MFMA throughout', 'b2': 'dW on 2-way-split bf16 operands (2^-16 per product), dX chain on the fp32 MFMA',
-                                       'b2x': 'dW and the dX chain on 2-way-split bf16 operands (2^-16 relative per product, fp32 accumulate; '
-                                              '1.0e-5 of max against a float64 statement away from ReLU kinks: profiles/r04_mlp_bwd_denc_outlier.txt), '
-                                              'forward recompute in fp32 (3-way split)',
-                                       'b2f': 'as b2x with the forward recompute on 2-way-split bf16 operands',
-                                       'h2f': 'forward recompute with the forward\'s own arithmetic (2-way fp16 split), dW and the dX chain on 2-way-split '
-                                              'bf16 operands (2^-16 relative per product), fp32 accumulate'}.get(os.environ.get('XR_MLP_BWD_DW', 'h2f'), 'see XR_MLP_BWD_DW')
-                                      if ops._mlp_mode() != 1 else 'fp16 operands, fp32 accumulate'),
-                       'rays_per_step': rays_all / args.steps / world, 'samples_per_ray': samples_all / max(rays_all, 1),
-                       'samples_per_s': samples_all / elapsed_max, 'n_images': args.n_img,
-                       'preroll_iterations': preroll, 'timed_iterations': [it0, it1 - 1], 'grid_refreshes_in_window': n_refresh,
-                       'device_ms_normal_iteration': sum(ms_normal) / max(len(ms_normal), 1),
-                       'device_ms_refresh_iteration': sum(ms_refresh) / max(len(ms_refresh), 1) if ms_refresh else None,
-                       'rays_per_batch_history': hist,
-                       'parallelism': 'ray-sharded data parallel x%d, gradient all-reduce (RCCL)' % world if world > 1 else 'single GPU'},
+        out = headline_line()
+        out.update({
             'roofline': roof,
-            'mlp_range_events': mlp_range_events,
             'roofline_kernels': roofs,
             'backward_live_row_fraction': {'timed_window': live_frac_timed, 'kernel_window': live_frac_win,
                                            'note': 'share of the marched samples whose dL/d(raw) is not exactly zero (T == 0 behind opaque '
                                                    'surfaces makes the rest exact zeros); the MLP backward and the table scatter process '
                                                    'these rows only, results are identical to the backward over every row'},
-        }
+        })
         out.update(extra)
         # secondary measurements must never cost the headline line: a failure is reported in place of the numbers
         def guarded(key, fn):

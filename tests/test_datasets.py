@@ -102,32 +102,45 @@ def write_llff_scene(root, n=7, H=12, W=16, factor=4):
     np.save(os.path.join(root, 'poses_bounds.npy'), np.array(rows))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'xrnerf')), reason='reference tree absent')
-@pytest.mark.parametrize('kw', [dict(recenter=True, bd_factor=.75, spherify=False, path_zflat=False),
-                                dict(recenter=True, bd_factor=.75, spherify=True, path_zflat=False),
-                                dict(recenter=False, bd_factor=None, spherify=False, path_zflat=False)])
-def test_load_llff_data_equals_the_reference(tmp_path, kw):
-    """the reference's own load_llff_data (imageio replaced by PIL: it is absent here) on a forward-facing rig written
-    on the fly, all three pose-normalisation variants"""
+LLFF_VARIANTS = [dict(recenter=True, bd_factor=.75, spherify=False, path_zflat=False),
+                 dict(recenter=True, bd_factor=.75, spherify=True, path_zflat=False),
+                 dict(recenter=False, bd_factor=None, spherify=False, path_zflat=False)]
+
+
+def reference_load_llff(root, kw):
+    """the reference's own load_llff_data on `root` (imageio replaced by PIL: it is absent here); needs the reference tree"""
     from PIL import Image
-    from xrnerf_amd.datasets import load_llff_data
-    write_llff_scene(str(tmp_path))
     imageio = types.ModuleType('imageio'); imageio.imread = lambda f, **k: np.asarray(Image.open(f))
     saved = sys.modules.get('imageio')
     sys.modules['imageio'] = imageio
     try:
         spec = importlib.util.spec_from_file_location('ref_load_llff', os.path.join(REF, 'xrnerf/datasets/load_data/load_llff.py'))
         ref = importlib.util.module_from_spec(spec); spec.loader.exec_module(ref)
-        b = ref.load_llff_data(str(tmp_path), factor=4, **kw)
+        return ref.load_llff_data(root, factor=4, **kw)
     finally:
         if saved is None: sys.modules.pop('imageio', None)
         else: sys.modules['imageio'] = saved
+
+
+@pytest.mark.parametrize('kw', LLFF_VARIANTS)
+def test_load_llff_data_equals_the_reference(tmp_path, kw):
+    """the reference's own load_llff_data on a forward-facing rig written on the fly, all three pose-normalisation variants:
+    against its recorded outputs (tests/golden/ref_llff.npz, made by tests/golden/make_golden_llff.py) and, where the
+    reference tree is present, against the function itself"""
+    from xrnerf_amd.datasets import load_llff_data
+    write_llff_scene(str(tmp_path))
     a = load_llff_data(str(tmp_path), factor=4, **kw)
-    assert a[0].shape == b[0].shape == (7, 12, 16, 3) and np.array_equal(a[0], b[0])
-    for k in (1, 2, 3):
-        assert a[k].shape == b[k].shape and a[k].dtype == np.float32
-        assert np.allclose(a[k], b[k], atol=1e-6 * max(1.0, np.abs(b[k]).max())), k
-    assert a[4] == int(b[4])
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_llff.npz'))
+    v = LLFF_VARIANTS.index(kw)
+    refs = [[gold['v%d_%d' % (v, k)] for k in range(5)]]
+    if os.path.isdir(os.path.join(REF, 'xrnerf')):
+        refs.append(reference_load_llff(str(tmp_path), kw))
+    for b in refs:
+        assert a[0].shape == b[0].shape == (7, 12, 16, 3) and np.array_equal(a[0], b[0])
+        for k in (1, 2, 3):
+            assert a[k].shape == b[k].shape and a[k].dtype == np.float32
+            assert np.allclose(a[k], b[k], atol=1e-6 * max(1.0, np.abs(b[k]).max())), k
+        assert a[4] == int(b[4])
     assert a[1][0, 0, 4] == 12 and a[1][0, 1, 4] == 16 and abs(a[1][0, 2, 4] - 75.0) < 1e-6       # hwf column, focal / factor
 
 

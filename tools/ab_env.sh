@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 V=$1; shift
 for val in "$@"; do
   if [ "$val" = unset ]; then unset $V; else export $V=$val; fi
-  python bench.py --steps 64 --warmup 5 --no-cpu-baseline --no-mip --no-kilo --no-unbounded --no-f16 --no-strict --no-extra --no-render > /tmp/ab.json 2>/dev/null
+  python bench.py --full --steps 64 --warmup 5 --no-cpu-baseline --no-mip --no-kilo --no-unbounded --no-f16 --no-strict --no-extra --no-render > /tmp/ab.json 2>/dev/null
   python - <<PY
 import json
 d=json.loads(open('/tmp/ab.json').read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ for st in "$@"; do
   case $name in
     tests)   timeout 1200 python -m pytest tests -m gpu -q -x --durations=8 $arg 2>&1 | tail -30 | tee $O/${TAG}_pytest_gpu.txt ;;
     smoke)   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 | tee $O/${TAG}_smoke.txt ;;
-    bench)   timeout 1200 python bench.py ${arg:---steps 20 --warmup 5} > $O/${TAG}_bench.json 2> $O/${TAG}_bench_err.txt; tail -c 300 $O/${TAG}_bench_err.txt
+    bench)   timeout 1200 python bench.py --full ${arg:---steps 20 --warmup 5} > $O/${TAG}_bench.json 2> $O/${TAG}_bench_err.txt; tail -c 300 $O/${TAG}_bench_err.txt
              python tools/benchsum.py $O/${TAG}_bench.json ;;
     kstats)  (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- \
                python $R/bench.py ${arg:---steps 128 --warmup 5 --no-cpu-baseline --no-mip --no-kilo --no-unbounded --no-render --no-f16 --no-strict --no-extra} > /tmp/b.log 2>&1; tail -c 300 /tmp/b.log)
