@@ -690,6 +690,39 @@ int xr_linear_backward_bias(const float* dy, const float* mask_src, uint32_t M, 
  * one launch at memory speed (torch's `partials.sum(0)` took 17 us per 67-MB set of a 256 x 256 layer, this 11).  out is WRITTEN. */
 int xr_sum_partials(const float* partials, uint32_t n_partials, size_t stride, uint32_t n, float* out, void* stream);
 
+/* KiloNeRF distillation (the reference's StudentNerfNetwork / KiloNerfMultiNetwork / KiloNerfSimpleRender and the occupancy hook).
+ * Students: the tiny MLPs of xr_kilo_mlp_forward, same packed blocks params [N, param_stride]; n_hidden in [1, 2], pos_freqs <= 10,
+ * dir_freqs <= 4.  examples [N, batch, ex_stride] device, grouped by network: position (global) 0..2, direction 3..5.
+ *   xr_kilo_student_step: one launch, workgroup = network: local coordinates (domain_mins / domain_maxs [N, 3]), Fourier features,
+ *     the MLP, the renders (teacher_raw [N, batch, 4]: sigmoid / 1 - exp(-relu(sigma) alpha_distance); the students: the same with
+ *     leaky_relu), loss[N] = mean over examples of the mean over the 4 channels of the squared error (nullable), and the gradient
+ *     of sum(loss) -- WRITTEN to grad [N, param_stride] (nullable when adam_step > 0 and batch <= 128).  adam_step > 0: the
+ *     torch.optim.Adam update (no weight decay, bias correction of step adam_step) of params / adam_m / adam_v in the same launch.
+ *     No float atomics: the sums over the examples run in a fixed order, so two calls on the same inputs give the same bits.
+ *   xr_kilo_student_forward: out [N, n_examples, 4] = raw, or with render != 0 the rendered [sigmoid(rgb), alpha] (leaky_relu);
+ *     domain_mins == domain_maxs == NULL: the positions are local coordinates already.
+ *   xr_kilo_distill_examples: examples [N, batch, ex_stride] (channels 0..5 written): example b of every network takes the index
+ *     PCG32(seed, iteration, b) mod pool_size; the example (uniform point in the network's box, unit direction = a normalised
+ *     Gaussian) is PCG32(seed, network, index) -- a pool of pool_size examples per network that is never stored.
+ *   xr_kilo_occupancy_points: points [n_voxels, prod(sub), 3] of voxels [voxel_begin, voxel_begin + n_voxels) of the row-major grid
+ *     res (host arrays of 3): torch.linspace over the first voxel (sub points per axis, both edges) + index * voxel size, in the fp32
+ *     operation order of build_occupancy_tree_hook.py (the same bits).
+ *   xr_kilo_occupancy_reduce: occupancy[v] = any over its samples_per_voxel rows of raw[row * raw_stride + 3] > threshold (1 byte,
+ *     the layout KiloNerfMLP reads).  No host synchronisation in any of them. */
+int xr_kilo_student_step(const float* examples, uint32_t ex_stride, const float* teacher_raw, const float* domain_mins,
+                         const float* domain_maxs, float* params, uint32_t param_stride, uint32_t num_networks, uint32_t batch,
+                         int pos_freqs, int dir_freqs, int n_hidden, float alpha_distance, float* loss, float* grad,
+                         float* adam_m, float* adam_v, int adam_step, float lr, float beta1, float beta2, float eps, void* stream);
+int xr_kilo_student_forward(const float* examples, uint32_t ex_stride, uint32_t n_examples, const float* domain_mins,
+                            const float* domain_maxs, const float* params, uint32_t param_stride, uint32_t num_networks,
+                            int pos_freqs, int dir_freqs, int n_hidden, int render, float alpha_distance, float* out, void* stream);
+int xr_kilo_distill_examples(uint64_t seed, uint64_t iteration, uint64_t pool_size, const float* domain_mins, const float* domain_maxs,
+                             uint32_t num_networks, uint32_t batch, uint32_t ex_stride, float* examples, void* stream);
+int xr_kilo_occupancy_points(const float* gmin_host, const float* gmax_host, const int32_t* res_host, const int32_t* sub_host,
+                             uint64_t voxel_begin, uint32_t n_voxels, float* points, void* stream);
+int xr_kilo_occupancy_reduce(const float* raw, uint32_t raw_stride, uint32_t samples_per_voxel, float threshold, uint32_t n_voxels,
+                             uint8_t* occupancy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

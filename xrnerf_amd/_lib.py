@@ -155,6 +155,12 @@ SIGNATURES = {
     'xr_kilo_render_workspace_bytes': (_sz, [_u32, _u32, _u32]),
     'xr_kilo_render_rays': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32,
                                    _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'xr_kilo_student_step': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _f, _f,
+                                    _f, _f, _vp]),
+    'xr_kilo_student_forward': (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _i32, _i32, _i32, _i32, _f, _vp, _vp]),
+    'xr_kilo_distill_examples': (_i32, [_u64, _u64, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    'xr_kilo_occupancy_points': (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    'xr_kilo_occupancy_reduce': (_i32, [_vp, _u32, _u32, _f, _u32, _vp, _vp]),
 }
 
 _lib = None

@@ -23,6 +23,7 @@
 // Bound: fp32 MFMA (157.3 TFLOP/s; 12.2 kflop per evaluated sample + 3 padded K slots per Fourier group) for
 // k_kilo_mlp, HBM for the rest.
 #include "xr_common.h"
+#include "xr_adam.h"            // adam1: the students' fused update
 #include "xr_mip_math.h"      // xr_mip_zval: GetZvals' linspace (datasets/pipelines/create.py:502-516)
 
 #define KILO_H 32            // hidden width == direction-layer width of every reference config
@@ -948,6 +949,484 @@ extern "C" int xr_nerf_render_forward(const float* raw, const float* z_vals, con
     hipLaunchKernelGGL(k_nerf_render, dim3(xr_div_up(n_rays, 4)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4*>(raw), zr, (const int32_t*)nullptr, (const uint32_t*)nullptr, white_bkgd, rgb,
                        disp, acc, weights);
+    XR_LAUNCH_CHECK();
+    return XR_OK;
+}
+
+// ------------------------------------------------------------------------------------------ distillation: student networks
+// KiloNeRF's middle phase (the reference: models/networks/student_nerf.py, mlps/kilonerf_multinet.py, renders/
+// kilonerf_simple_render.py, datasets/kilonerf_node_dataset.py, core/hooks/build_occupancy_tree_hook.py).  The students are the
+// tiny MLPs above in the same packed block layout; their examples are grouped by network ([N, B, stride]: position xyz,
+// direction xyz), so a workgroup owns one network and never searches for it.
+//   k_kilo_student_step   workgroup = network: local coordinates, Fourier features, the MLP (the MFMA chain of k_kilo_mlp),
+//                         both renders (teacher: relu, student: leaky_relu -- KiloNerfSimpleRender on 2-D / 3-D raw), the
+//                         network's MSE, and the backward pass of k_kilo_mlp_bwd.  No float atomics: each wave stores its
+//                         contribution to a range of the gradient block in a stage slot of its own, and after a barrier the
+//                         workgroup adds the four slots in a fixed order -- the same bits on every run.  The gradient range is
+//                         complete then, so the optional Adam update of those floats (params / m / v read and written once) is
+//                         applied in the same pass.
+//   k_kilo_student_fwd    workgroup = (128 examples, network): forward only, raw or rendered
+//   k_kilo_distill_examples  thread = (network, example): uniform points in the network's box, unit directions from normalised
+//                         Gaussians; PCG32 keyed by (seed, iteration, example) for the example index shared by all networks,
+//                         and by (seed, network, index) for the example itself (a virtual pool of pool_size examples per network)
+//   k_kilo_occ_points / k_kilo_occ_reduce  the occupancy grid's sub-voxel lattice (the hook's fp32 operation order) and
+//                         any(sigma > threshold) per voxel
+// Bound: k_kilo_student_step is a dependent fp32-MFMA chain per wave (4 waves per network, ~1 workgroup per CU: LDS); the others
+// are HBM-bound element-wise passes.
+#define KS_SLOT 1104                             // floats per wave's stage slot: the largest gradient range (alpha + feature: 1092)
+
+struct KiloStudentArgs {
+    const float* ex; uint32_t ex_stride, batch;  // examples [N, batch, ex_stride]: position 0..2, direction 3..5
+    const float* teacher_raw;                     // [N, batch, 4] (step only)
+    const float* domain_mins; const float* domain_maxs;   // [N, 3]; NULL (forward only): positions are local already
+    float* params; uint32_t param_stride, num_networks;
+    int pos_freqs, dir_freqs;
+    float alpha_distance;
+    float* loss; float* grad;                     // [N]; [N, param_stride] (nullable with Adam and batch <= 128)
+    float* m; float* v; int adam; float b1, b2, step_size, bc2s, eps;
+};
+
+template <int NH> struct KiloStudentAct { f32x16 h0, hl, feat, hd; float o[3], alpha; };
+
+struct KiloBlockOffsets {
+    int P, D, b0, l1, alpha, feat, dir, bd, rgb, end;
+    __device__ KiloBlockOffsets(int pf, int df, int nh) {
+        P = 3 * (2 * pf + 1); D = 3 * (2 * df + 1);
+        b0 = P * KILO_H; l1 = b0 + KILO_H; alpha = l1 + (nh - 1) * (KILO_H * KILO_H + KILO_H);
+        feat = alpha + KILO_H + 4; dir = feat + KILO_H * KILO_H + KILO_H;
+        bd = dir + (KILO_H + D) * KILO_H; rgb = bd + KILO_H; end = rgb + 4 * KILO_H + 4;
+    }
+};
+
+// MultiNetwork.forward (late_feed_direction, relu) for the wave's 32 examples, every activation kept for the backward pass
+template <int NH>
+__device__ __forceinline__ void kilo_student_forward(const float* __restrict__ w, const KiloBlockOffsets& o, const float x[3],
+                                                     const float v[3], int pf, int df, int col, int hi, KiloStudentAct<NH>& f) {
+    f32x16 acc = kilo_bias(w + o.b0, hi);
+    for (int c = 0; c < 3; ++c) acc = kilo_feed_fourier(w + c * (2 * pf + 1) * KILO_H, acc, x[c], pf, col, hi);
+    f.h0 = kilo_relu(acc);
+    f.hl = f.h0;
+    if (NH == 2) f.hl = kilo_relu(kilo_dense32(w + o.l1, kilo_bias(w + o.l1 + KILO_H * KILO_H, hi), f.h0, col, hi));
+    float alpha = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) alpha = fmaf(w[o.alpha + kdrow(r) + 4 * hi], f.hl[r], alpha);
+    f.alpha = alpha + __shfl_xor(alpha, 32, 64) + w[o.alpha + KILO_H];
+    f.feat = kilo_dense32(w + o.feat, kilo_bias(w + o.feat + KILO_H * KILO_H, hi), f.hl, col, hi);
+    acc = kilo_dense32(w + o.dir, kilo_bias(w + o.bd, hi), f.feat, col, hi);
+    for (int c = 0; c < 3; ++c) acc = kilo_feed_fourier(w + o.dir + (KILO_H + c * (2 * df + 1)) * KILO_H, acc, v[c], df, col, hi);
+    f.hd = kilo_relu(acc);
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float4 t = *reinterpret_cast<const float4*>(w + o.rgb + (kdrow(r) + 4 * hi) * 4);
+        o0 = fmaf(t.x, f.hd[r], o0); o1 = fmaf(t.y, f.hd[r], o1); o2 = fmaf(t.z, f.hd[r], o2);
+    }
+    const float4 br = *reinterpret_cast<const float4*>(w + o.rgb + KILO_H * 4);
+    f.o[0] = o0 + __shfl_xor(o0, 32, 64) + br.x;
+    f.o[1] = o1 + __shfl_xor(o1, 32, 64) + br.y;
+    f.o[2] = o2 + __shfl_xor(o2, 32, 64) + br.z;
+}
+
+__device__ __forceinline__ float kilo_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float kilo_leaky(float x) { return x > 0.f ? x : x * 0.01f; }     // F.leaky_relu, slope 0.01
+
+// position (local coordinates, transforms.py:35-45) and direction of example `ei` of network `net`
+__device__ __forceinline__ void kilo_student_inputs(const KiloStudentArgs& a, uint32_t net, size_t ei, float x[3], float v[3]) {
+    const float* e = a.ex + ei * a.ex_stride;
+    for (int c = 0; c < 3; ++c) {
+        if (a.domain_mins != nullptr) {
+            const float lo = a.domain_mins[net * 3 + c], hi_d = a.domain_maxs[net * 3 + c];
+            x[c] = 2.f * (e[c] - lo) / (hi_d - lo) - 1.f;
+        } else {
+            x[c] = e[c];
+        }
+        v[c] = e[3 + c];
+    }
+}
+
+// one wave's share of a gradient range, plain LDS stores into its stage slot (S = the slot at the range's first float)
+__device__ __forceinline__ void kst_tile(float* __restrict__ S, const f32x16& d, int ldw, int n_rows, int n_cols, int col, int hi) {
+    if (col < n_cols) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = kdrow(r) + 4 * hi;
+            if (k < n_rows) S[k * ldw + col] = d[r];
+        }
+    }
+}
+__device__ __forceinline__ void kst_bias(float* __restrict__ S, const f32x16& d, int col, int hi) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float sum = khalf_sum(d[r]);
+        if (col == 0) S[kdrow(r) + 4 * hi] = sum;
+    }
+}
+__device__ __forceinline__ void kst_zero(float* __restrict__ S, int n, int lane) {
+    for (int j = lane; j < n; j += 64) S[j] = 0.f;
+    __builtin_amdgcn_wave_barrier();                 // the zeros land before the other lanes' contributions
+}
+// the workgroup adds the four slots of gradient range [g0, g1) in a fixed order (+ the earlier rounds' sum, kept in grad) and,
+// on the last round, writes the gradient and / or applies Adam to those floats
+__device__ __forceinline__ void kst_flush(const KiloStudentArgs& a, const float* __restrict__ stage, uint32_t net, int g0, int g1,
+                                          bool first, bool last) {
+    __syncthreads();
+    const size_t base = (size_t)net * a.param_stride;
+    for (int e = g0 + (int)threadIdx.x; e < g1; e += (int)blockDim.x) {
+        const int j = e - g0;
+        float g = (stage[j] + stage[KS_SLOT + j]) + (stage[2 * KS_SLOT + j] + stage[3 * KS_SLOT + j]);
+        if (!first) g = a.grad[base + e] + g;
+        if (a.grad != nullptr) a.grad[base + e] = g;
+        if (last && a.adam) {
+            float p = a.params[base + e], m = a.m[base + e], v = a.v[base + e];
+            adam1(p, g, m, v, a.b1, a.b2, a.step_size, a.bc2s, a.eps, 0.f);
+            a.params[base + e] = p; a.m[base + e] = m; a.v[base + e] = v;
+        }
+    }
+    __syncthreads();
+}
+
+template <int NH>
+__global__ void __launch_bounds__(64 * KB_WAVES) k_kilo_student_step(KiloStudentArgs a) {
+    extern __shared__ float s_w[];                      // [parameter block | per-wave tiles | per-wave stage slots]
+    __shared__ float s_loss[KB_WAVES];
+    const uint32_t net = blockIdx.x;
+    const int pf = a.pos_freqs, df = a.dir_freqs;
+    const KiloBlockOffsets o(pf, df, NH);
+    const uint32_t n_floats = (uint32_t)o.end;
+    const int lane = threadIdx.x & 63, col = lane & 31, hi = lane >> 5;
+    const uint32_t wave = threadIdx.x >> 6;
+    float* tin = s_w + n_floats + wave * KB_WAVE_FLOATS;
+    float* tdl = tin + 64 * KB_ST;
+    const float* stage = s_w + n_floats + KB_WAVES * KB_WAVE_FLOATS;
+    float* slot = s_w + n_floats + KB_WAVES * KB_WAVE_FLOATS + wave * KS_SLOT;
+    {
+        const float4* src = reinterpret_cast<const float4*>(a.params + (size_t)net * a.param_stride);
+        float4* dst = reinterpret_cast<float4*>(s_w);
+        for (uint32_t q = threadIdx.x; q < n_floats / 4; q += 64 * KB_WAVES) dst[q] = src[q];
+    }
+    __syncthreads();
+    const float* w = s_w;
+    const float ad = a.alpha_distance, dscale = 2.f / (4.f * (float)a.batch);      // d mean(mean((out - t)^2, 2), 1) / d out
+    const uint32_t rounds = (a.batch + KILO_TILE - 1) / KILO_TILE;
+    float loss_acc = 0.f;
+    for (uint32_t round = 0; round < rounds; ++round) {
+        const bool first = round == 0, last = round + 1 == rounds;
+        const uint32_t b = round * KILO_TILE + wave * 32 + col;
+        const bool live = b < a.batch;
+        const size_t ei = (size_t)net * a.batch + (live ? b : a.batch - 1);
+        float x[3], v[3];
+        kilo_student_inputs(a, net, ei, x, v);
+        KiloStudentAct<NH> f;
+        kilo_student_forward<NH>(w, o, x, v, pf, df, col, hi, f);
+        // renders (KiloNerfSimpleRender): teacher raw is 2-D (relu), the students' 3-D (leaky_relu); then the MSE and its gradient
+        float gr[4] = {0.f, 0.f, 0.f, 0.f}, ls = 0.f;
+        if (live) {
+            const float* t = a.teacher_raw + ei * 4;
+            float err[4], dsig[4];
+            for (int c = 0; c < 3; ++c) {
+                const float s = kilo_sigmoid(f.o[c]);
+                err[c] = s - kilo_sigmoid(t[c]);
+                dsig[c] = s * (1.f - s);
+            }
+            const float la = kilo_leaky(f.alpha), ea = expf(-la * ad);
+            err[3] = (1.f - ea) - (1.f - expf(-fmaxf(t[3], 0.f) * ad));
+            dsig[3] = ea * ad * (f.alpha > 0.f ? 1.f : 0.01f);
+            ls = (((err[0] * err[0] + err[1] * err[1]) + err[2] * err[2]) + err[3] * err[3]) / 4.f;
+            for (int c = 0; c < 4; ++c) gr[c] = (dscale * err[c]) * dsig[c];
+        }
+        {
+            const float lsum = khalf_sum(ls);
+            if (lane == 0) s_loss[wave] = lsum;
+        }
+        // ---- gradient range 1: direction-layer Fourier rows, its bias, the rgb head
+        int g0 = o.dir + KILO_H * KILO_H;
+        kst_zero(slot, o.end - g0, lane);
+        f32x16 d;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) d[r] = 0.f;
+        if (hi == 0) { d[0] = gr[0]; d[1] = gr[1]; d[2] = gr[2]; }
+        ktile_to_lds(tin, f.hd, col, hi);
+        ktile_to_lds(tdl, d, col, hi);
+        kst_tile(slot + (o.rgb - g0), kouter(tin, tdl, col, hi), 4, KILO_H, 3, col, hi);
+        {
+            const float s0 = khalf_sum(gr[0]), s1 = khalf_sum(gr[1]), s2 = khalf_sum(gr[2]);
+            if (lane == 0) { slot[o.rgb + KILO_H * 4 - g0] = s0; slot[o.rgb + KILO_H * 4 + 1 - g0] = s1; slot[o.rgb + KILO_H * 4 + 2 - g0] = s2; }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float4 t = *reinterpret_cast<const float4*>(w + o.rgb + (kdrow(r) + 4 * hi) * 4);
+            d[r] = f.hd[r] > 0.f ? fmaf(t.x, gr[0], fmaf(t.y, gr[1], t.z * gr[2])) : 0.f;
+        }
+        ktile_to_lds(tdl, d, col, hi);
+        for (int rr = hi; rr < 32; rr += 2) tin[rr * KB_ST + col] = 0.f;
+        __builtin_amdgcn_wave_barrier();
+        for (int c = 0; c < 3; ++c) kfourier_to_lds(tin + c * (2 * df + 1) * KB_ST, v[c], df, col, hi);
+        kst_tile(slot + (o.dir + KILO_H * KILO_H - g0), kouter(tin, tdl, col, hi), KILO_H, o.D, KILO_H, col, hi);
+        kst_bias(slot + (o.bd - g0), d, col, hi);
+        kst_flush(a, stage, net, g0, o.end, first, last);
+        if (threadIdx.x == 0) loss_acc += (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
+        // ---- range 2: direction-layer feature rows
+        g0 = o.dir;
+        ktile_to_lds(tin, f.feat, col, hi);
+        kst_tile(slot, kouter(tin, tdl, col, hi), KILO_H, KILO_H, KILO_H, col, hi);
+        kst_flush(a, stage, net, g0, o.dir + KILO_H * KILO_H, first, last);
+        d = kilo_dense32_T(w + o.dir, d, col, hi);                      // dL/dfeature (no activation)
+        // ---- range 3: alpha head (+ its 3 pad floats), feature layer
+        g0 = o.alpha;
+        kst_zero(slot, o.dir - g0, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float sum = khalf_sum(f.hl[r] * gr[3]);
+            if (col == 0) slot[kdrow(r) + 4 * hi] = sum;
+        }
+        {
+            const float s3 = khalf_sum(gr[3]);
+            if (lane == 0) slot[KILO_H] = s3;
+        }
+        ktile_to_lds(tdl, d, col, hi);
+        ktile_to_lds(tin, f.hl, col, hi);
+        kst_tile(slot + (o.feat - g0), kouter(tin, tdl, col, hi), KILO_H, KILO_H, KILO_H, col, hi);
+        kst_bias(slot + (o.feat + KILO_H * KILO_H - g0), d, col, hi);
+        kst_flush(a, stage, net, g0, o.dir, first, last);
+        d = kilo_dense32_T(w + o.feat, d, col, hi);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) d[r] = f.hl[r] > 0.f ? fmaf(w[o.alpha + kdrow(r) + 4 * hi], gr[3], d[r]) : 0.f;
+        // ---- range 4: second hidden layer
+        if (NH == 2) {
+            ktile_to_lds(tdl, d, col, hi);
+            ktile_to_lds(tin, f.h0, col, hi);
+            kst_tile(slot, kouter(tin, tdl, col, hi), KILO_H, KILO_H, KILO_H, col, hi);
+            kst_bias(slot + KILO_H * KILO_H, d, col, hi);
+            kst_flush(a, stage, net, o.l1, o.alpha, first, last);
+            d = kilo_dense32_T(w + o.l1, d, col, hi);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d[r] = f.h0[r] > 0.f ? d[r] : 0.f;
+        }
+        // ---- ranges 5 (and 6): first layer on the positions' Fourier features, rows >= 32 with the bias, then rows < 32
+        ktile_to_lds(tdl, d, col, hi);
+        for (int rr = hi; rr < 64; rr += 2) tin[rr * KB_ST + col] = 0.f;
+        __builtin_amdgcn_wave_barrier();
+        for (int c = 0; c < 3; ++c) kfourier_to_lds(tin + c * (2 * pf + 1) * KB_ST, x[c], pf, col, hi);
+        if (o.P > 32) {
+            g0 = 32 * KILO_H;
+            kst_tile(slot, kouter(tin + 32 * KB_ST, tdl, col, hi), KILO_H, o.P - 32, KILO_H, col, hi);
+            kst_bias(slot + (o.b0 - g0), d, col, hi);
+            kst_flush(a, stage, net, g0, o.l1, first, last);
+            kst_tile(slot, kouter(tin, tdl, col, hi), KILO_H, 32, KILO_H, col, hi);
+            kst_flush(a, stage, net, 0, g0, first, last);
+        } else {
+            kst_tile(slot, kouter(tin, tdl, col, hi), KILO_H, o.P, KILO_H, col, hi);
+            kst_bias(slot + o.b0, d, col, hi);
+            kst_flush(a, stage, net, 0, o.l1, first, last);
+        }
+    }
+    if (threadIdx.x == 0 && a.loss != nullptr) a.loss[net] = loss_acc / (float)a.batch;
+}
+
+template <int NH>
+__global__ void __launch_bounds__(256) k_kilo_student_fwd(KiloStudentArgs a, float* __restrict__ out, int render) {
+    extern __shared__ float s_w[];
+    const uint32_t net = blockIdx.y;
+    const int pf = a.pos_freqs, df = a.dir_freqs;
+    const KiloBlockOffsets o(pf, df, NH);
+    const int lane = threadIdx.x & 63, col = lane & 31, hi = lane >> 5;
+    const uint32_t wave = threadIdx.x >> 6;
+    {
+        const float4* src = reinterpret_cast<const float4*>(a.params + (size_t)net * a.param_stride);
+        float4* dst = reinterpret_cast<float4*>(s_w);
+        for (uint32_t q = threadIdx.x; q < (uint32_t)o.end / 4; q += 256) dst[q] = src[q];
+    }
+    __syncthreads();
+    const uint32_t wave0 = blockIdx.x * KILO_TILE + wave * 32;
+    if (wave0 >= a.batch) return;                       // (uniform per wave; no barrier below)
+    const uint32_t b = wave0 + col;
+    const bool live = b < a.batch;
+    const size_t ei = (size_t)net * a.batch + (live ? b : a.batch - 1);
+    float x[3], v[3];
+    kilo_student_inputs(a, net, ei, x, v);
+    KiloStudentAct<NH> f;
+    kilo_student_forward<NH>(s_w, o, x, v, pf, df, col, hi, f);
+    if (live && hi == 0) {
+        float4 r = make_float4(f.o[0], f.o[1], f.o[2], f.alpha);
+        if (render) r = make_float4(kilo_sigmoid(f.o[0]), kilo_sigmoid(f.o[1]), kilo_sigmoid(f.o[2]),
+                                    1.f - expf(-kilo_leaky(f.alpha) * a.alpha_distance));
+        out[ei * 4 + 0] = r.x; out[ei * 4 + 1] = r.y; out[ei * 4 + 2] = r.z; out[ei * 4 + 3] = r.w;
+    }
+}
+
+__device__ __forceinline__ float kilo_gauss_pair(xr_pcg32& r, float* second) {
+    const float u1 = r.next_float(), u2 = r.next_float();
+    const float rad = sqrtf(-2.f * logf(1.f - u1));                 // 1 - u1 in (0, 1]
+    float s, c;
+    sincosf(6.28318530718f * u2, &s, &c);
+    *second = rad * s;
+    return rad * c;
+}
+
+__global__ void __launch_bounds__(256) k_kilo_distill_examples(uint64_t seed, uint64_t iteration, uint64_t pool_size,
+                                                               const float* __restrict__ domain_mins, const float* __restrict__ domain_maxs,
+                                                               uint32_t num_networks, uint32_t batch, uint32_t ex_stride,
+                                                               float* __restrict__ ex) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)num_networks * batch) return;
+    const uint32_t net = (uint32_t)(t / batch), b = (uint32_t)(t - (uint64_t)net * batch);
+    xr_pcg32 r;
+    r.seed(seed ^ 0x9e3779b97f4a7c15ull, iteration);     // ExampleSample: one index per example slot, shared by all networks
+    r.advance(b);
+    const uint64_t idx = r.next_uint() % pool_size;
+    r.seed(seed, ((uint64_t)net << 32) | idx);           // the example itself: a function of (network, index)
+    float* e = ex + t * ex_stride;
+    for (int c = 0; c < 3; ++c) {
+        const float lo = domain_mins[net * 3 + c], hi = domain_maxs[net * 3 + c];
+        e[c] = lo + (hi - lo) * r.next_float();
+    }
+    float g[4];
+    g[0] = kilo_gauss_pair(r, &g[1]);
+    g[2] = kilo_gauss_pair(r, &g[3]);
+    float n2 = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+    if (!(n2 > 1e-30f)) { g[0] = 0.f; g[1] = 0.f; g[2] = 1.f; n2 = 1.f; }
+    const float inv = 1.f / sqrtf(n2);
+    for (int c = 0; c < 3; ++c) e[3 + c] = g[c] * inv;
+}
+
+#define KILO_OCC_MAX_SUB 16
+struct KiloOccLattice {
+    float first[3][KILO_OCC_MAX_SUB];   // torch.linspace(first_voxel_min, first_voxel_max, sub) per axis, evaluated on the host
+    float voxel[3];                      // occupancy voxel size
+    uint32_t res[3], sub[3];
+};
+
+// build_occupancy_tree_hook.py:56-77: points[v][s] = first_voxel_samples[s] + index(v) * occupancy_voxel_size
+__global__ void __launch_bounds__(256) k_kilo_occ_points(KiloOccLattice L, uint64_t voxel_begin, uint32_t n_voxels, float* __restrict__ pts) {
+    const uint32_t S = L.sub[0] * L.sub[1] * L.sub[2];
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)n_voxels * S) return;
+    const uint64_t vl = t / S, vox = voxel_begin + vl;
+    const uint32_t s = (uint32_t)(t - vl * S);
+    const uint64_t idx[3] = {vox / ((uint64_t)L.res[1] * L.res[2]), (vox / L.res[2]) % L.res[1], vox % L.res[2]};
+    const uint32_t sid[3] = {s / (L.sub[1] * L.sub[2]), (s / L.sub[2]) % L.sub[1], s % L.sub[2]};
+    for (int c = 0; c < 3; ++c) pts[t * 3 + c] = L.first[c][sid[c]] + (float)idx[c] * L.voxel[c];
+}
+
+__global__ void __launch_bounds__(256) k_kilo_occ_reduce(const float* __restrict__ raw, uint32_t raw_stride, uint32_t samples_per_voxel,
+                                                         float threshold, uint32_t n_voxels, uint8_t* __restrict__ occ) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_voxels) return;
+    bool any = false;
+    for (uint32_t s = 0; s < samples_per_voxel; ++s) any = any || raw[((uint64_t)t * samples_per_voxel + s) * raw_stride + 3] > threshold;
+    occ[t] = any ? 1 : 0;
+}
+
+static int kilo_student_check(const float* ex, uint32_t ex_stride, const float* params, uint32_t param_stride, uint32_t num_networks,
+                              uint32_t batch, int pos_freqs, int dir_freqs, int n_hidden) {
+    XR_REQUIRE(ex && params, "null pointer");
+    XR_REQUIRE(ex_stride >= 6, "ex_stride must be >= 6 (position, direction)");
+    XR_REQUIRE(num_networks >= 1 && num_networks <= 65535 && batch >= 1, "network count in [1, 65535], batch >= 1");
+    XR_REQUIRE(n_hidden >= 1 && n_hidden <= 2 && pos_freqs >= 0 && pos_freqs <= 10 && dir_freqs >= 0 && dir_freqs <= 4,
+               "students: n_hidden in [1, 2], pos_freqs <= 10, dir_freqs <= 4 (the architectures of the reference configs)");
+    XR_REQUIRE(param_stride >= kilo_param_floats(pos_freqs, dir_freqs, n_hidden) && param_stride % 4 == 0 && ((uintptr_t)params & 15) == 0,
+               "param_stride too small / not a multiple of 4 floats, or params not 16-byte aligned");
+    return XR_OK;
+}
+
+extern "C" int xr_kilo_student_step(const float* examples, uint32_t ex_stride, const float* teacher_raw, const float* domain_mins,
+                                    const float* domain_maxs, float* params, uint32_t param_stride, uint32_t num_networks, uint32_t batch,
+                                    int pos_freqs, int dir_freqs, int n_hidden, float alpha_distance, float* loss, float* grad,
+                                    float* adam_m, float* adam_v, int adam_step, float lr, float beta1, float beta2, float eps,
+                                    void* stream) {
+    const int rc = kilo_student_check(examples, ex_stride, params, param_stride, num_networks, batch, pos_freqs, dir_freqs, n_hidden);
+    if (rc) return rc;
+    XR_REQUIRE(teacher_raw && domain_mins && domain_maxs, "null pointer");
+    XR_REQUIRE(adam_step <= 0 || (adam_m && adam_v), "Adam needs its moments");
+    XR_REQUIRE(grad != nullptr || (adam_step > 0 && batch <= KILO_TILE), "grad may be NULL only with Adam and batch <= 128");
+    KiloStudentArgs a{examples, ex_stride, batch, teacher_raw, domain_mins, domain_maxs, params, param_stride, num_networks,
+                      pos_freqs, dir_freqs, alpha_distance, loss, grad, adam_m, adam_v, adam_step > 0 ? 1 : 0, beta1, beta2, 0.f, 1.f, eps};
+    if (adam_step > 0) {                                 // torch.optim.Adam: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t)
+        a.step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)adam_step)));
+        a.bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)adam_step));
+    }
+    const size_t lds = ((size_t)kilo_param_floats(pos_freqs, dir_freqs, n_hidden) + (size_t)KB_WAVES * (KB_WAVE_FLOATS + KS_SLOT)) * 4;
+    XR_REQUIRE(lds <= 96 * 1024, "parameter block + the waves' tiles and stage slots do not fit the LDS");
+    static bool attr = false;
+    if (!attr) {
+        XR_HIP(hipFuncSetAttribute((const void*)k_kilo_student_step<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        XR_HIP(hipFuncSetAttribute((const void*)k_kilo_student_step<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr = true;
+    }
+    if (n_hidden == 1) hipLaunchKernelGGL(k_kilo_student_step<1>, dim3(num_networks), dim3(64 * KB_WAVES), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_kilo_student_step<2>, dim3(num_networks), dim3(64 * KB_WAVES), lds, (hipStream_t)stream, a);
+    XR_LAUNCH_CHECK();
+    return XR_OK;
+}
+
+extern "C" int xr_kilo_student_forward(const float* examples, uint32_t ex_stride, uint32_t n_examples, const float* domain_mins,
+                                       const float* domain_maxs, const float* params, uint32_t param_stride, uint32_t num_networks,
+                                       int pos_freqs, int dir_freqs, int n_hidden, int render, float alpha_distance, float* out,
+                                       void* stream) {
+    if (n_examples == 0) return XR_OK;
+    const int rc = kilo_student_check(examples, ex_stride, params, param_stride, num_networks, n_examples, pos_freqs, dir_freqs, n_hidden);
+    if (rc) return rc;
+    XR_REQUIRE(out != nullptr && (domain_mins == nullptr) == (domain_maxs == nullptr), "null pointer");
+    KiloStudentArgs a{examples, ex_stride, n_examples, nullptr, domain_mins, domain_maxs, const_cast<float*>(params), param_stride,
+                      num_networks, pos_freqs, dir_freqs, alpha_distance, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const size_t lds = (size_t)kilo_param_floats(pos_freqs, dir_freqs, n_hidden) * 4;
+    const dim3 grid(xr_div_up(n_examples, KILO_TILE), num_networks);
+    if (n_hidden == 1) hipLaunchKernelGGL(k_kilo_student_fwd<1>, grid, dim3(256), lds, (hipStream_t)stream, a, out, render);
+    else hipLaunchKernelGGL(k_kilo_student_fwd<2>, grid, dim3(256), lds, (hipStream_t)stream, a, out, render);
+    XR_LAUNCH_CHECK();
+    return XR_OK;
+}
+
+extern "C" int xr_kilo_distill_examples(uint64_t seed, uint64_t iteration, uint64_t pool_size, const float* domain_mins,
+                                        const float* domain_maxs, uint32_t num_networks, uint32_t batch, uint32_t ex_stride,
+                                        float* examples, void* stream) {
+    const uint64_t n = (uint64_t)num_networks * batch;
+    if (n == 0) return XR_OK;
+    XR_REQUIRE(domain_mins && domain_maxs && examples, "null pointer");
+    XR_REQUIRE(ex_stride >= 6 && pool_size >= 1 && pool_size <= (1ull << 32) && num_networks < (1u << 31), "ex_stride >= 6, pool_size in [1, 2^32]");
+    hipLaunchKernelGGL(k_kilo_distill_examples, dim3((uint32_t)xr_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, seed, iteration,
+                       pool_size, domain_mins, domain_maxs, num_networks, batch, ex_stride, examples);
+    XR_LAUNCH_CHECK();
+    return XR_OK;
+}
+
+extern "C" int xr_kilo_occupancy_points(const float* gmin_host, const float* gmax_host, const int32_t* res_host, const int32_t* sub_host,
+                                        uint64_t voxel_begin, uint32_t n_voxels, float* points, void* stream) {
+    XR_REQUIRE(gmin_host && gmax_host && res_host && sub_host, "null host pointer");
+    KiloOccLattice L;
+    uint64_t total = 1;
+    for (int c = 0; c < 3; ++c) {
+        XR_REQUIRE(res_host[c] >= 1 && sub_host[c] >= 1 && sub_host[c] <= KILO_OCC_MAX_SUB, "resolution >= 1, subsample resolution in [1, 16]");
+        L.res[c] = (uint32_t)res_host[c]; L.sub[c] = (uint32_t)sub_host[c];
+        total *= L.res[c];
+        // the hook's fp32 tensor ops, one rounding each: size = max - min, voxel = size / res, first max = min + voxel, then
+        // torch.linspace (start + step * i below the middle, end - step * (steps - i - 1) from it on)
+        volatile float size = gmax_host[c] - gmin_host[c];
+        volatile float vx = size / (float)res_host[c];
+        volatile float start = gmin_host[c], end = start + vx;
+        L.voxel[c] = vx;
+        const int steps = sub_host[c];
+        if (steps == 1) { L.first[c][0] = start; continue; }
+        volatile float step = (end - start) / (float)(steps - 1);
+        for (int i = 0; i < steps; ++i) {
+            volatile float val = i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
+            L.first[c][i] = val;
+        }
+    }
+    if (n_voxels == 0) return XR_OK;
+    XR_REQUIRE(points != nullptr && voxel_begin + n_voxels <= total, "null pointer / voxel range past the grid");
+    const uint64_t n = (uint64_t)n_voxels * L.sub[0] * L.sub[1] * L.sub[2];
+    hipLaunchKernelGGL(k_kilo_occ_points, dim3((uint32_t)xr_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, L, voxel_begin, n_voxels, points);
+    XR_LAUNCH_CHECK();
+    return XR_OK;
+}
+
+extern "C" int xr_kilo_occupancy_reduce(const float* raw, uint32_t raw_stride, uint32_t samples_per_voxel, float threshold,
+                                        uint32_t n_voxels, uint8_t* occupancy, void* stream) {
+    if (n_voxels == 0) return XR_OK;
+    XR_REQUIRE(raw && occupancy && raw_stride >= 4 && samples_per_voxel >= 1, "null pointer / raw_stride < 4");
+    hipLaunchKernelGGL(k_kilo_occ_reduce, dim3(xr_div_up(n_voxels, 256)), dim3(256), 0, (hipStream_t)stream, raw, raw_stride,
+                       samples_per_voxel, threshold, n_voxels, occupancy);
     XR_LAUNCH_CHECK();
     return XR_OK;
 }
