@@ -726,4 +726,5 @@ int xr_kilo_occupancy_reduce(const float* raw, uint32_t raw_stride, uint32_t sam
 #ifdef __cplusplus
 }
 #endif
+#include "xrnerf_mi355_bungee.h"
 #endif

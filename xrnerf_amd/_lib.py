@@ -163,6 +163,16 @@ SIGNATURES = {
     'xr_kilo_occupancy_reduce': (_i32, [_vp, _u32, _u32, _f, _u32, _vp, _vp]),
 }
 
+# BungeeNeRF (csrc/xr_bungee.hip, declared in include/xrnerf_mi355_bungee.h).  A table of its own: SIGNATURES binds xrnerf_mi355.h's
+# declarations one to one, and the host emulation (tests/hip_emu) maps it onto the host builds of the sources it knows;
+# tests/test_emu_bungee.py adds xr_bungee's host build and this table on top.
+BUNGEE_SIGNATURES = {
+    'xr_bungee_zvals': (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp, _f, _f, _f, _vp, _vp]),
+    'xr_bungee_encode': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _i32, _i32, _i32, _vp, _u32, _vp, _u32, _vp]),
+    'xr_bungee_render_forward': (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _i32, _f, _f, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'xr_bungee_render_backward': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _i32, _f, _f, _i32, _i32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -218,7 +228,7 @@ def load():
                 finally:
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -1464,3 +1464,101 @@ def linear_backward_bias(dy, mask_src):
     part = torch.empty((splits, N), dtype=torch.float32, device=dy.device)
     _lib.check(L.xr_linear_backward_bias(_ptr(dy), _ptr(mask_src), M, N, splits, _ptr(part), _stream()), 'xr_linear_backward_bias')
     return sum_partials(part)
+
+
+# ---------------------------------------------------------------- BungeeNeRF (configs/bungeenerf/bungeenerf_multiscale_google.py)
+_BUNGEE_BOUNDS = {None: 0, 'none': 0, 'sphere': 1, 'flat': 2}
+EARTH_RADIUS = 6371011.0              # metres, as BungeeGetBounds; buildings are assumed below 250 m
+
+
+def bungee_zvals(rays_o, viewdirs, near, far, n_z, ray_nearfar='sphere', scene_origin=(0., 0., 0.), scaling=1.0):
+    """BungeeGetBounds + BungeeGetZvals in one launch -> (near [R,1], far [R,1], z_vals [R,n_z]).  With ray_nearfar 'sphere' / 'flat'
+    near / far are computed (the arguments may be None); with None / 'none' they are inputs."""
+    mode = _BUNGEE_BOUNDS[ray_nearfar]
+    dev = viewdirs.device if viewdirs is not None else near.device
+    R = (viewdirs if mode else near.reshape(-1)).shape[0]
+    if mode:
+        near = torch.empty((R, 1), dtype=torch.float32, device=dev)
+        far = torch.empty((R, 1), dtype=torch.float32, device=dev)
+    else:
+        near, far = _f32c(near.reshape(R, 1)).clone(), _f32c(far.reshape(R, 1)).clone()
+    z = torch.empty((R, n_z), dtype=torch.float32, device=dev)
+    s = float(scaling)
+    # the reference's float64 scalars, rounded to fp32 where its tensor ops round them
+    gc = (C.c_float * 3)(*[float(v) * s for v in scene_origin])
+    r2_top = ((EARTH_RADIUS + 250.0) * s) ** 2
+    r2_earth = (EARTH_RADIUS * s) ** 2
+    with _span('xr_bungee_zvals', R):
+        _lib.check(_lib.load().xr_bungee_zvals(_ptr(_f32c(rays_o)) if mode else None, _ptr(_f32c(viewdirs)) if mode else None,
+                                               _ptr(near), _ptr(far), R, n_z, mode, C.cast(gc, C.c_void_p), r2_top, r2_earth, s,
+                                               _ptr(z), _stream()), 'xr_bungee_zvals')
+    return near, far, z
+
+
+def bungee_encode(viewdirs, multires, multires_dirs, frustum=None, gaussians=None, ray_shape='cone', out=None):
+    """cast_rays + BungeeEmbedder.forward -> [M, 3+6 multires + 3+6 multires_dirs] (the reference's data['embedded']): a column range of
+    a buffer whose rows are 16-byte aligned, so the MLP's linear kernels read it in place.  frustum = (rays_o, rays_d, radii, z_vals)
+    or gaussians = (means, covs) [R, S, 3]: exactly one."""
+    if (frustum is None) == (gaussians is None):
+        raise _lib.XrError('bungee_encode: give exactly one of frustum and gaussians')
+    R = viewdirs.shape[0]
+    if frustum is not None:
+        o, d, radii, z = frustum
+        S = z.shape[1] - 1
+        ptrs = (_ptr(_f32c(o)), _ptr(_f32c(d)), _ptr(_f32c(radii.reshape(-1))), _ptr(_f32c(z)), None, None)
+    else:
+        means, covs = gaussians
+        S = means.shape[1]
+        ptrs = (None, None, None, None, _ptr(_f32c(means)), _ptr(_f32c(covs)))
+    cp, cd = 3 + 6 * multires, 3 + 6 * multires_dirs
+    if out is None:
+        out = torch.empty((R * S, (cp + cd + 3) // 4 * 4), dtype=torch.float32, device=viewdirs.device)
+    if not _on_device(out) or out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[1] < cp + cd:
+        raise _lib.XrError('bungee_encode: out must be a float32 device matrix with contiguous rows of >= %d channels' % (cp + cd))
+    base = out.data_ptr()
+    with _span('xr_bungee_encode', R * S):
+        _lib.check(_lib.load().xr_bungee_encode(*ptrs, _ptr(_f32c(viewdirs)), R, S, multires, multires_dirs,
+                                                {'cone': 0, 'cylinder': 1}[ray_shape], C.c_void_p(base), out.stride(0),
+                                                C.c_void_p(base + 4 * cp), out.stride(0), _stream()), 'xr_bungee_encode')
+    return out[:, :cp + cd]
+
+
+def _bungee_render_common(raw, z_vals, viewdirs, noise):
+    R, n_z = z_vals.shape
+    raw = _f32c(raw)
+    if raw.dim() != 4 or tuple(raw.shape[:2]) != (R, n_z - 1) or raw.shape[3] != 4:
+        raise _lib.XrError('raw must be [R, n_z-1, heads, 4]')
+    if noise is not None:
+        noise = _f32c(noise)
+        assert tuple(noise.shape) == (R, n_z - 1)
+    return raw, _f32c(z_vals), _f32c(viewdirs), noise, R, n_z, raw.shape[2]
+
+
+def bungee_render_forward(raw, z_vals, viewdirs, stage, density_bias=-1.0, rgb_padding=0.0, white_bkgd=False,
+                          density_activation='softplus', noise=None):
+    """BungeeNerfRender.forward: raw [R,S,H,4] -> rgb [R,3], disp [R], acc [R], weights [R,S]"""
+    raw, z_vals, viewdirs, noise, R, n_z, H = _bungee_render_common(raw, z_vals, viewdirs, noise)
+    dev = raw.device
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    disp = torch.empty((R,), dtype=torch.float32, device=dev)
+    acc = torch.empty((R,), dtype=torch.float32, device=dev)
+    w = torch.empty((R, n_z - 1), dtype=torch.float32, device=dev)
+    with _span('xr_bungee_render_forward', R * (n_z - 1)):
+        _lib.check(_lib.load().xr_bungee_render_forward(_ptr(raw), _ptr(z_vals), _ptr(viewdirs), _ptr(noise), R, n_z, H, int(stage),
+                                                        float(density_bias), float(rgb_padding), int(bool(white_bkgd)),
+                                                        _MIP_ACT[density_activation], _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(w),
+                                                        _stream()), 'xr_bungee_render_forward')
+    return rgb, disp, acc, w
+
+
+def bungee_render_backward(raw, z_vals, viewdirs, grad_rgb, stage, density_bias=-1.0, rgb_padding=0.0, white_bkgd=False,
+                           density_activation='softplus', noise=None):
+    """dL/draw [R,S,H,4] given dL/drgb: equal for heads <= stage, zeros above"""
+    raw, z_vals, viewdirs, noise, R, n_z, H = _bungee_render_common(raw, z_vals, viewdirs, noise)
+    out = torch.empty_like(raw)
+    with _span('xr_bungee_render_backward', R * (n_z - 1)):
+        _lib.check(_lib.load().xr_bungee_render_backward(_ptr(raw), _ptr(z_vals), _ptr(viewdirs), _ptr(noise), _ptr(_f32c(grad_rgb)), R,
+                                                         n_z, H, int(stage), float(density_bias), float(rgb_padding),
+                                                         int(bool(white_bkgd)), _MIP_ACT[density_activation], _ptr(out), _stream()),
+                   'xr_bungee_render_backward')
+    return out
