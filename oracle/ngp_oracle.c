@@ -555,6 +555,37 @@ void xo_hashgrid_bwd(const float* x, const float* dy, int n, int n_levels, const
     }
 }
 
+/* Test infrastructure for the float64 table-gradient reference: the 8 corners every sample touches on levels [l0, l1).  The cell and
+ * the fractional position come from the fp32 arithmetic of xo_hashgrid_fwd (so the cell is the kernels'); the trilinear weights
+ * are multiplied in double from those fp32 fractions.  idx [n, l1 - l0, 8] = absolute table ENTRY (offset[l] + the level's index,
+ * dense, hashed and upper-face wrap-around alike), w [n, l1 - l0, 8]. */
+void xo_hashgrid_corners(const float* x, int n, int l0, int l1, const float* scale, const uint32_t* resolution,
+                         const uint32_t* offset, int64_t* idx, double* w) {
+    const int nl = l1 - l0;
+#pragma omp parallel for num_threads(g_threads) if (g_threads > 1)
+    for (int i = 0; i < n; ++i) {
+        for (int l = l0; l < l1; ++l) {
+            uint32_t hsize = offset[l + 1] - offset[l];
+            float f[3]; uint32_t g[3];
+            for (int d = 0; d < 3; ++d) {
+                float p = x[3 * (size_t)i + d] * scale[l] + 0.5f;
+                float fl = floorf(p);
+                g[d] = (uint32_t)(int)fl; f[d] = p - fl;
+            }
+            size_t o = ((size_t)i * nl + (l - l0)) * 8;
+            for (int c = 0; c < 8; ++c) {
+                double wt = 1.0; uint32_t q[3];
+                for (int d = 0; d < 3; ++d) {
+                    if ((c & (1 << d)) == 0) { wt *= 1.0 - (double)f[d]; q[d] = g[d]; }
+                    else { wt *= (double)f[d]; q[d] = g[d] + 1u; }
+                }
+                idx[o + c] = (int64_t)offset[l] + (int64_t)xo_grid_index(q[0], q[1], q[2], resolution[l], hsize);
+                w[o + c] = wt;
+            }
+        }
+    }
+}
+
 /* SH degree 4 on d' = 2*x - 1 (x is the reference's warp_direction output in [0,1]) -> 16 values */
 void xo_sh4(const float* dirs, int n, float* out) {
 #pragma omp parallel for num_threads(g_threads) if (g_threads > 1)

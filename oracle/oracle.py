@@ -292,6 +292,20 @@ def hashgrid_bwd(x, dy, meta):
     return g
 
 
+def hashgrid_corners(x, meta, levels=None):
+    """-> idx int64 [n, L, 8] (absolute table entries), w float64 [n, L, 8]: the corners each position touches on the levels
+    `levels=(l0, l1)` (default all), cell chosen with xo_hashgrid_fwd's fp32 arithmetic, weights multiplied in double
+    (xo_hashgrid_corners)"""
+    x = _f32(x)
+    n = x.shape[0]
+    l0, l1 = (0, meta.n_levels) if levels is None else levels
+    idx = np.zeros((n, l1 - l0, 8), np.int64)
+    w = np.zeros((n, l1 - l0, 8), np.float64)
+    port().xo_hashgrid_corners(_p(x), C.c_int(n), C.c_int(l0), C.c_int(l1), _p(meta.scale), _p(meta.resolution),
+                               _p(meta.offset), _p(idx), _p(w))
+    return idx, w
+
+
 def sh4(dirs):
     dirs = _f32(dirs)
     out = np.zeros((dirs.shape[0], 16), np.float32)

@@ -6,6 +6,9 @@ import pytest
 import torch
 
 from conftest import grad_close
+import grad_bars as B
+import ref64_ngp as R
+import test_gpu_backward_f64 as F64
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +50,8 @@ def test_hashgrid_fwd_bwd(O, dev, n):
     ops.hashgrid_bwd(T(x, dev), dt.contiguous(), meta, g)
     err = np.abs(g.cpu().numpy() - ref_g).max()
     assert err <= 1e-4 * max(1.0, np.abs(ref_g).max()), err
+    if n >= 16384:                       # the binned / run-length scatter: every entry against its own float64 bound
+        B.scatter_close(g.cpu().numpy(), R.table_grad64(O, x, dy, om), meta, dy, n, what='uniform n=%d' % n)
     # the atomic scatter (no workspace) and the LDS-partition scan (n >= 16384, hashed levels) agree
     g1 = torch.zeros_like(g)
     ops.hashgrid_bwd(T(x, dev), dt.contiguous(), meta, g1, use_workspace=False)
@@ -265,6 +270,7 @@ def test_default_backward_on_kink_free_rows_at_the_plain_bar(O, dev, n, monkeypa
     ops.hashgrid_bwd(tp, denc_t, meta, g_t)
     for name, got, ref in (('wd', g_wd, gd), ('wc', g_wc, gc), ('table', g_t, gt)):
         grad_close(got.cpu().numpy(), ref, name, kinks=False)
+    F64.backward_against_float64(O, dev, table, wd, wc, pts, dirs, draw)
 
 
 def test_nerf_mlp_fwd_asymmetric_weights(O, dev, f32_forward):
@@ -313,6 +319,7 @@ def test_nerf_mlp_bwd(O, dev, n):
     for name, got, ref in (('wd', g_wd, gd), ('wc', g_wc, gc), ('table', g_t, gt)):
         # both sides sum n fp32 terms in different orders (the oracle serially): ~sqrt(n)*2^-24 relative
         grad_close(got.cpu().numpy(), ref, name)
+    F64.backward_against_float64(O, dev, table, wd, wc, pts, dirs, draw)
 
 
 @pytest.mark.parametrize('arith', ['f32', 'b2', 'b2x', 'h2f'])
@@ -396,6 +403,7 @@ def test_deeper_topologies_against_the_oracle(O, dev, nhd, nhc, n, n_valid, path
     ops.hashgrid_bwd(tp, denc_t, meta, g_t, n_dev=n_dev)
     for name, got, refg in (('wd', g_wd, gd), ('wc', g_wc, gc), ('table', g_t, gt)):
         grad_close(got.cpu().numpy(), refg, name, kinks=True)
+    F64.backward_against_float64(O, dev, table, wd, wc, pts, dirs, draw, nhd, nhc, n_valid)
 
 
 def test_streamed_kernels_equal_the_layer_by_layer_path_at_full_size(dev, monkeypatch):
