@@ -259,9 +259,10 @@ __device__ __forceinline__ int hslot(int m, int ns) {           // offset of neu
     const int e = (m & 3) | (((m >> 3) & 1) << 2), hi = (m >> 2) & 1, t = m >> 4;
     return (hi * ns + t) * 8 + e;
 }
-// dW on the bf16 matrix cores (XR_MLP_BWD_DW=b2, review item 3 of round 2): the same staging tile, each operand read as 8
-// consecutive samples of one neuron and split in registers into two bf16 parts x = xh + xl (xh = bf16(x) round-to-nearest,
-// xl = bf16(x - xh), the difference exact in fp32).  Three v_mfma_f32_32x32x16_bf16 per 16 samples keep
+// dW on the bf16 matrix cores (XR_MLP_BWD_DW=b2, review item 3 of round 2): each operand is 8 consecutive samples of one neuron in
+// two bf16 parts x = xh + xl (xh = bf16(x) round-to-nearest, xl = bf16(x - xh), the difference exact in fp32) -- split before the
+// staging in k_nerf_mlp_bwd_1_2 (dws_store below), behind the read of the fp32 staging tile in the deep kernel (split2x8).
+// Three v_mfma_f32_32x32x16_bf16 per 16 samples keep
 // gh*hh + gh*hl + gl*hh (every bf16 x bf16 product exact, fp32 accumulate, small terms first); the dropped gl*hl term and the
 // rounding of the low parts are below 2^-16 of |g||h| per term -- inside the 1e-3 * max bar the gradients are tested to
 // (tests/test_gpu_tcnn.py::test_nerf_mlp_bwd*).  6 matrix instructions of 8 passes instead of 16 of 16 per output tile.
@@ -279,59 +280,6 @@ __device__ __forceinline__ void split2x8(const float* __restrict__ p, bw8& h, bw
         l[e] = (__bf16)(v - (float)hh);
     }
 }
-template <int TO, int TI>
-__device__ __forceinline__ void dw_mfma_b2(f32x16 (&acc)[TO][TI], const float* __restrict__ stage, int col, int hi) {
-    const float* sg = stage + col * ST33 + 8 * hi;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        bw8 ah[TO], al[TO], bh[TI], bl[TI];
-#pragma unroll
-        for (int to = 0; to < TO; ++to) split2x8(sg + (to * 32) * ST33 + 16 * t, ah[to], al[to]);
-#pragma unroll
-        for (int ti = 0; ti < TI; ++ti) split2x8(sg + ((TO + ti) * 32) * ST33 + 16 * t, bh[ti], bl[ti]);
-#pragma unroll
-        for (int to = 0; to < TO; ++to)
-#pragma unroll
-            for (int ti = 0; ti < TI; ++ti) {
-                acc[to][ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[to], bh[ti], acc[to][ti], 0, 0, 0);
-                acc[to][ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[to], bl[ti], acc[to][ti], 0, 0, 0);
-                acc[to][ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[to], bh[ti], acc[to][ti], 0, 0, 0);
-            }
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-template <bool B2, int TO, int TI>
-__device__ __forceinline__ void dw_product(f32x16 (&acc)[TO][TI], const float* __restrict__ stage, int col, int hi) {
-    if constexpr (B2) dw_mfma_b2<TO, TI>(acc, stage, col, hi);
-    else dw_mfma<TO, TI>(acc, stage, col, hi);
-}
-// one H tile at a time (the c1 layer under the 3-tile staging area of the bf16 dX mode): acc[.][TIX] += G (tiles 0..TO-1 of the
-// staging area) x H (tile TO)
-template <int TO, int TIA, int TIX>
-__device__ __forceinline__ void dw_mfma_b2_col(f32x16 (&acc)[TO][TIA], const float* __restrict__ stage, int col, int hi) {
-    const float* sg = stage + col * ST33 + 8 * hi;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        bw8 ah[TO], al[TO], bh, bl;
-#pragma unroll
-        for (int to = 0; to < TO; ++to) split2x8(sg + (to * 32) * ST33 + 16 * t, ah[to], al[to]);
-        split2x8(sg + (TO * 32) * ST33 + 16 * t, bh, bl);
-#pragma unroll
-        for (int to = 0; to < TO; ++to) {
-            acc[to][TIX] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[to], bh, acc[to][TIX], 0, 0, 0);
-            acc[to][TIX] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[to], bl, acc[to][TIX], 0, 0, 0);
-            acc[to][TIX] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[to], bh, acc[to][TIX], 0, 0, 0);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-// staging-area tile `slot` <- one tile (transposing write, as dw_stage)
-__device__ __forceinline__ void dw_stage_one(const f32x16& h, int slot, float* __restrict__ stage, int col, int hi) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) stage[(slot * 32 + drow(r) + 4 * hi) * ST33 + col] = h[r];
-    __builtin_amdgcn_wave_barrier();
-}
-
 // dX chain on the bf16 matrix cores (XR_MLP_BWD_DW=b2x): W^T sits in LDS pre-split into two bf16 parts, each in the
 // [in neuron][hi][K-step][8] arrangement of the fp16 kernels; a gradient tile goes from the accumulator layout to the B
 // operands of its two K-steps by a register-local 2-way split (the k-slot permutation is the accumulator layout's own row
@@ -349,6 +297,75 @@ __device__ __forceinline__ B2Tile to_b2(const f32x16& t) {
         r.p[0][1][e] = h1; r.p[1][1][e] = (__bf16)(t[8 + e] - (float)h1);
     }
     return r;
+}
+// dW staging in 16-bit form (k_nerf_mlp_bwd_1_2, every mode whose dW runs on the bf16 matrix cores).  A tile is split ONCE, in
+// registers (to_b2); the pair feeds the dX chain and this stage, nothing is split again behind an LDS read.  Per wave and staged
+// tile: S[part][sample][neuron] bf16 with 64-byte rows, written as the values sit in the accumulator layout -- lane (sample col,
+// half hi) holds neurons 16 k + 8 j + 4 hi + (0..3) in elements 4 j .. 4 j + 3 of p[part][k], one 8-byte store each, 8 per tile --
+// and read back turned round by ds_read_b64_tr_b16 (lane mapping: profiles/r02_ds_read_tr_b16_lane_mapping.txt; same use as
+// gkt_operand in xr_gemm.hip): two reads are the 8 consecutive samples of one neuron that a 32x32x16 operand wants.
+// Banks (derived from the per-instruction rules, ds_write_b64: 4 x 16 lanes over 32 banks, ds_read_b64_tr_b16: 2 x 32 lanes over
+// 64): plain 64-byte rows serve the reads (4 k-rows = 64 consecutive dwords) and make the stores 8-way (16 lanes = 16 rows at one
+// chunk, 16 dwords apart).  The 8-byte chunk index is therefore XORed with bits 1..3 of the sample: 16 rows at one chunk then hit
+// 8 chunk positions x 2 row parities = all 32 banks once, and a read still covers whole rows.
+#define DWS_ROW 32                               // halves per sample row
+#define DWS_PART (32 * DWS_ROW)                  // halves per part of a tile
+#define DWS_TILE (2 * DWS_PART)                  // halves per staged tile (4 096 B)
+typedef short dws4 __attribute__((ext_vector_type(4)));
+typedef short dws8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ int dws_off(int row, int chunk) { return row * DWS_ROW + 4 * (chunk ^ ((row >> 1) & 7)); }
+// staging-area tile `slot` <- one split tile; the caller puts a wave barrier between the last store and the first read
+__device__ __forceinline__ void dws_store(const B2Tile& x, int slot, __bf16* __restrict__ stage, int col, int hi) {
+    dws8 v[2][2];
+    __builtin_memcpy(v, x.p, sizeof(v));
+#pragma unroll
+    for (int part = 0; part < 2; ++part)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const dws4 q = {v[part][k][4 * j], v[part][k][4 * j + 1], v[part][k][4 * j + 2], v[part][k][4 * j + 3]};
+                *reinterpret_cast<dws4*>(stage + slot * DWS_TILE + part * DWS_PART + dws_off(col, 4 * k + 2 * j + hi)) = q;
+            }
+}
+// the operand of K-step t (samples 16 t + 8 hi + 0..7 of neuron col) out of one part of a staged tile.  Every lane of the wave
+// must take part (the read gathers across lanes): callers keep it outside lane-divergent control flow.
+__device__ __forceinline__ bw8 dws_operand(const __bf16* __restrict__ part, int t, int col, int hi) {
+    const int row = 16 * t + 8 * hi + ((col & 15) >> 2), chunk = 4 * (col >> 4) + (col & 3);
+    const dws4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(XR_LDS_PTR(dws4, part + dws_off(row, chunk)));
+    const dws4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16(XR_LDS_PTR(dws4, part + dws_off(row + 4, chunk)));
+    const dws8 v = {lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
+    bw8 out;
+    __builtin_memcpy(&out, &v, sizeof(out));
+    return out;
+}
+// acc[to][TI0 + ti] += G (staged tiles 0 .. TO-1) x H (staged tiles TO .. TO+TI-1): element e of K-step
+// t in lane half hi is sample 16 t + 8 hi + e, lo.hi, hi.lo, hi.hi per accumulator -- on operands that arrive already split
+template <int TO, int TIA, int TI = TIA, int TI0 = 0>
+__device__ __forceinline__ void dws_mfma(f32x16 (&acc)[TO][TIA], const __bf16* __restrict__ stage, int col, int hi) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        bw8 ah[TO], al[TO], bh[TI], bl[TI];
+#pragma unroll
+        for (int to = 0; to < TO; ++to) {
+            ah[to] = dws_operand(stage + to * DWS_TILE, t, col, hi);
+            al[to] = dws_operand(stage + to * DWS_TILE + DWS_PART, t, col, hi);
+        }
+#pragma unroll
+        for (int ti = 0; ti < TI; ++ti) {
+            bh[ti] = dws_operand(stage + (TO + ti) * DWS_TILE, t, col, hi);
+            bl[ti] = dws_operand(stage + (TO + ti) * DWS_TILE + DWS_PART, t, col, hi);
+        }
+#pragma unroll
+        for (int to = 0; to < TO; ++to)
+#pragma unroll
+            for (int ti = 0; ti < TI; ++ti) {
+                acc[to][TI0 + ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[to], bh[ti], acc[to][TI0 + ti], 0, 0, 0);
+                acc[to][TI0 + ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[to], bl[ti], acc[to][TI0 + ti], 0, 0, 0);
+                acc[to][TI0 + ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[to], bh[ti], acc[to][TI0 + ti], 0, 0, 0);
+            }
+    }
+    __builtin_amdgcn_wave_barrier();
 }
 template <int NH, int L>
 __device__ __forceinline__ void store_layer_bt2(const float (&v)[NetShape<NH>::out_rows_lds(L) * NetShape<NH>::in_dim(L) / MLP_THREADS],
@@ -665,6 +682,41 @@ __device__ __forceinline__ void sh4_eval(float x, float y, float z, float* o) {
     o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
 }
 
+// The same terms for k_nerf_mlp_bwd_1_2, with every fused multiply-add SPELLED OUT.  sh4_eval above leaves fusing to the compiler
+// (this file is built with contraction allowed), and which of `a*b + c*d`'s products it fuses depends on the code around the call:
+// every kernel's binary evaluates terms 9, 14 and 15 its own way, one ulp apart, and restaging the backward's dW operands moved them
+// (dWc changed in the last bits, dL/d(encoding) and dWd did not).  Pinned here is what the backward's binaries evaluated before that
+// change, so that its results stay the same bits whatever is edited around it: FUSE15 = false in every arithmetic but the bf16
+// recompute (MODE 3), whose binary fused term 15 and not term 9.  The host build (no contraction anywhere) keeps its plain products.
+__device__ __forceinline__ float sh_fma(float a, float b, float c) {
+#ifdef __HIP_EMU__
+    return a * b + c;
+#else
+    return __builtin_fmaf(a, b, c);
+#endif
+}
+template <bool FUSE15>
+__device__ __forceinline__ void sh4_eval_pinned(float x, float y, float z, float* o) {
+#pragma clang fp contract(off)
+    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+    o[0] = 0.28209479177387814f;
+    o[1] = -0.48860251190291987f * y;
+    o[2] = 0.48860251190291987f * z;
+    o[3] = -0.48860251190291987f * x;
+    o[4] = 1.0925484305920792f * xy;
+    o[5] = -1.0925484305920792f * yz;
+    o[6] = sh_fma(0.94617469575755997f, z2, -0.31539156525251999f);
+    o[7] = -1.0925484305920792f * xz;
+    o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
+    o[9] = 0.59004358992664352f * y * (FUSE15 ? -3.0f * x2 + y2 : sh_fma(-3.0f, x2, y2));
+    o[10] = 2.8906114426405538f * xy * z;
+    o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
+    o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
+    o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
+    o[14] = 1.4453057213202769f * z * sh_fma(-y, y, x2);
+    o[15] = 0.59004358992664352f * x * (FUSE15 ? sh_fma(-x, x, 3.0f * y2) : -x2 + 3.0f * y2);
+}
+
 // ---- per-tile pieces ---------------------------------------------------------------------------
 // Row r of the tile sits at enc_t + (drow(r) + 4 hi) * ld + s.  Written as a wave-uniform row base (scalar registers) plus ONE
 // 32-bit per-lane byte offset, so that the 16 accesses are `global_load_dword v, v_off, s[base]`: as sixteen per-lane 64-bit
@@ -683,11 +735,14 @@ __device__ __forceinline__ void store_enc_tile(float* __restrict__ denc_t, uint3
         *reinterpret_cast<float*>(reinterpret_cast<char*>(denc_t + (size_t)drow(r) * ld) + voff) = scale == 1.0f ? g[r] : g[r] * scale;
 }
 // color-net input tile in slot space from the density output tile + SH of the view direction
+// PIN: 0 = sh4_eval as the compiler fuses it; 1 / 2 = sh4_eval_pinned<false / true> (k_nerf_mlp_bwd_1_2)
+template <int PIN = 0>
 __device__ __forceinline__ void build_color_in(const f32x16& dout, const float* __restrict__ dirs, uint32_t dir_stride,
                                                uint32_t s, float pad_value, f32x16& cin, int hi) {
     const float* d = dirs + (size_t)s * dir_stride;
     float sh[16];
-    sh4_eval(d[0] * 2.f - 1.f, d[1] * 2.f - 1.f, d[2] * 2.f - 1.f, sh);
+    if constexpr (PIN == 0) sh4_eval(d[0] * 2.f - 1.f, d[1] * 2.f - 1.f, d[2] * 2.f - 1.f, sh);
+    else sh4_eval_pinned<PIN == 2>(d[0] * 2.f - 1.f, d[1] * 2.f - 1.f, d[2] * 2.f - 1.f, sh);      // d * 2 is exact: fused or not, the same value
 #pragma unroll
     for (int r = 0; r < 8; ++r) cin[r] = dout[r];
     if (hi == 0) cin[0] = pad_value;                       // slot 0 = pad (density row 0 is sigma, not an input)
@@ -841,10 +896,15 @@ __global__ __launch_bounds__(LIVE_THREADS) void k_live_fill(const float4* __rest
 // ------------------------------------------------------------------ backward kernel
 // Specialised for the reference topology family NHD = 1, NHC = 2 (density 32->64->16,
 // color 32->64->64->16): every activation and all 12 dW accumulator tiles stay in registers.
-// MODE 0: fp32 MFMA throughout; 1: dW products on the bf16 matrix cores (2-way split); 2 (default): the dX chain as well; 3: and the
-// forward recompute (no fp32 copy of the weights).  LDS per workgroup, bytes: fp32 weights 50 176 (modes 0-2) | W in two bf16 parts
-// 43 520 (mode 3); W^T in two bf16 parts 57 344 (modes 2-3); per-wave transposing stage 4 x 16 896 (modes 0-1) | 4 x 12 672 (modes 2-3):
-// 117 760 / 158 208 / 151 552 of the 163 840.
+// MODE 0: fp32 MFMA throughout; 1: dW products on the bf16 matrix cores (2-way split); 2: the dX chain as well; 3: and the
+// forward recompute on two bf16 parts (no fp32 copy of the weights); 4 (default): that recompute on two fp16 parts, the forward's own.
+// Modes 1-4 split every gradient and activation tile ONCE, in registers; the bf16 pair is the dX chain's operand and is staged for
+// dW in 16-bit form, read back through the transposing LDS load (dws_store / dws_operand / dws_mfma above).  The sums and their
+// order are those of the fp32 stage this replaced (split again behind every LDS read: 10 duplicate tile splits per sample tile),
+// so dW and dL/d(encoding) are the same bits (tests/test_gpu_mlp_bwd_bits.py; records: profiles/mlp_bwd_presplit_*.txt).
+// LDS per workgroup, bytes: fp32 weights 50 176 (modes 0-2) | W in two 16-bit parts 43 520 (modes 3-4); W^T in two bf16 parts
+// 57 344 (modes 2-4); per-wave dW stage 4 x 16 896 (mode 0: four fp32 tiles, stride 33) | 4 x 16 384 (mode 1: four 16-bit tiles)
+// | 4 x 12 288 (modes 2-4: three): 117 760 / 115 712 / 156 672 / 150 016 / 150 016 of the 163 840.
 template <bool LIVE, int MODE>
 __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
     const float* __restrict__ enc_t, uint32_t ld, const float* __restrict__ dirs, uint32_t dir_stride, uint32_t n,
@@ -856,6 +916,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
     using SD = NetShape<1>;
     using SC = NetShape<2>;
     constexpr int GW = SD::glb_floats + SC::glb_floats;                // 3072 + 7168
+    constexpr int SHPIN = MODE == 3 ? 2 : 1;                             // sh4_eval_pinned: the terms as each arithmetic's binary has always fused them
     constexpr bool DWB = MODE >= 1, DXB = MODE >= 2, FWB = MODE >= 3, FWH = MODE == 4;      // FWH: the recompute on two fp16 parts instead of two bf16 parts
     using HD = HShape<1>;
     using HC = HShape<2>;
@@ -863,7 +924,8 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
     using FC = F2Shape<2>;
     constexpr int PD = HD::b_halves, PC = HC::b_halves;                // halves per part of W^T
     constexpr int PFD = FD::halves, PFC = FC::halves;                  // halves per part of W (FWB)
-    constexpr int STAGE = (DXB ? 3 : 4) * 32 * ST33;                   // floats per wave
+    // per-wave dW stage, floats: fp32 [neuron][sample] tiles (mode 0) | 16-bit pre-split tiles (dws_store), 3 with the bf16 dX chain, else 4
+    constexpr int STAGE = DWB ? (DXB ? 3 : 4) * DWS_TILE / 2 : 4 * 32 * ST33;
     constexpr int W32 = FWB ? 0 : SD::lds_floats + SC::lds_floats;     // fp32 weights (none when the recompute is on bf16 too)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* wd = lds;
@@ -893,6 +955,10 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 31, hi = lane >> 5;
     float* stage = stage_all + wave * STAGE;
+    __bf16* bstage = reinterpret_cast<__bf16*>(stage);                 // DWB: the same area as 16-bit tiles
+    static_assert(STAGE % 4 == 0 && (DWS_ROW * sizeof(__bf16)) % 8 == 0 && (DWS_PART * sizeof(__bf16)) % 8 == 0,
+                  "8-byte alignment of every transposing read (a misaligned one returns the aligned address's data, silently)");
+    static_assert(LDS_FLOATS * sizeof(float) <= 163840, "the launch's LDS");
 
     f32x16 a_d0[2][1], a_d1[1][2], a_c0[2][1], a_c1[2][2], a_c2[1][2];   // dW accumulators
 #pragma unroll
@@ -920,7 +986,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
             { const H2Tile xb[1] = {to_h2(xe[0], H2_IN_SCALE)}; layer_fwd_h2<1, 2>(hfd + FD::off(0), PFD, xb, hd, col, hi); }
             h2_relu_sat(hd[0], 1.0f / H2_IN_SCALE); h2_relu_sat(hd[1], 1.0f / H2_IN_SCALE);     // relu + the input scale taken out again (exact)
             { const H2Tile hb[2] = {to_h2_act(hd[0]), to_h2_act(hd[1])}; layer_fwd_h2<2, 1, true>(hfd + FD::off(1), PFD, hb, dout, col, hi); }
-            build_color_in(dout[0], dirs, dir_stride, sc, pad_value, cin[0], hi);
+            build_color_in<SHPIN>(dout[0], dirs, dir_stride, sc, pad_value, cin[0], hi);
             { const H2Tile cb[1] = {to_h2(cin[0])}; layer_fwd_h2<1, 2>(hfc + FC::off(0), PFC, cb, hc1, col, hi); }
             h2_relu_sat(hc1[0]); h2_relu_sat(hc1[1]);
             { const H2Tile hb[2] = {to_h2_act(hc1[0]), to_h2_act(hc1[1])}; layer_fwd_h2<2, 2>(hfc + FC::off(1), PFC, hb, hc2, col, hi); }
@@ -929,7 +995,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
             { const B2Tile xb[1] = {to_b2(xe[0])}; layer_fwd_b2<1, 2>(wfd + FD::off(0), PFD, xb, hd, col, hi); }
             relu_tile(hd[0]); relu_tile(hd[1]);
             { const B2Tile hb[2] = {to_b2(hd[0]), to_b2(hd[1])}; layer_fwd_b2<2, 1, true>(wfd + FD::off(1), PFD, hb, dout, col, hi); }
-            build_color_in(dout[0], dirs, dir_stride, sc, pad_value, cin[0], hi);
+            build_color_in<SHPIN>(dout[0], dirs, dir_stride, sc, pad_value, cin[0], hi);
             { const B2Tile cb[1] = {to_b2(cin[0])}; layer_fwd_b2<1, 2>(wfc + FC::off(0), PFC, cb, hc1, col, hi); }
             relu_tile(hc1[0]); relu_tile(hc1[1]);
             { const B2Tile hb[2] = {to_b2(hc1[0]), to_b2(hc1[1])}; layer_fwd_b2<2, 2>(wfc + FC::off(1), PFC, hb, hc2, col, hi); }
@@ -938,7 +1004,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
             layer_fwd<1, 2, false>(wd + SD::lds_off(0), xe, hd, col, hi);
             relu_tile(hd[0]); relu_tile(hd[1]);
             layer_fwd<2, 1, false>(wd + SD::lds_off(1), hd, dout, col, hi);
-            build_color_in(dout[0], dirs, dir_stride, sc, pad_value, cin[0], hi);
+            build_color_in<SHPIN>(dout[0], dirs, dir_stride, sc, pad_value, cin[0], hi);
             layer_fwd<1, 2, false>(wc + SC::lds_off(0), cin, hc1, col, hi);
             relu_tile(hc1[0]); relu_tile(hc1[1]);
             layer_fwd<2, 2, false>(wc + SC::lds_off(1), hc1, hc2, col, hi);
@@ -953,32 +1019,56 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
         for (int r = 0; r < 16; ++r) g1[0][r] = 0.f;
         g1[0][0] = dr.x; g1[0][1] = dr.y; g1[0][2] = dr.z;             // hi==1 lanes hold zeros
         // color output layer
-        dw_stage<1, 2>(g1, hc2, stage, col, hi);
-        if constexpr (DXB) { const B2Tile gb[1] = {to_b2(g1[0])}; layer_bwd_b2<1, 2, 1>(wbc + HC::b_off(2), PC, gb, g2, col, hi); }
-        else layer_bwd<1, 2, false, 3>(wc + SC::lds_off(2), g1, g2, col, hi);   // rows 0..2 (rgb) only
-        dw_product<DWB, 1, 2>(a_c2, stage, col, hi);
+        if constexpr (DWB) {
+            // every G / H tile is split once (to_b2): the pair is staged for dW and, with DXB, is the dX chain's operand
+            const B2Tile gb[1] = {to_b2(g1[0])};
+            dws_store(gb[0], 0, bstage, col, hi); dws_store(to_b2(hc2[0]), 1, bstage, col, hi); dws_store(to_b2(hc2[1]), 2, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (DXB) layer_bwd_b2<1, 2, 1>(wbc + HC::b_off(2), PC, gb, g2, col, hi);
+            else layer_bwd<1, 2, false, 3>(wc + SC::lds_off(2), g1, g2, col, hi);
+            dws_mfma<1, 2>(a_c2, bstage, col, hi);
+        } else {
+            dw_stage<1, 2>(g1, hc2, stage, col, hi);
+            layer_bwd<1, 2, false, 3>(wc + SC::lds_off(2), g1, g2, col, hi);    // rows 0..2 (rgb) only
+            dw_mfma<1, 2>(a_c2, stage, col, hi);
+        }
         relu_mask(g2[0], hc2[0]); relu_mask(g2[1], hc2[1]);
         // color hidden layer 2
         if constexpr (DXB) {
             // 3-tile staging area: both G tiles and one H tile at a time
-            const f32x16 h0[1] = {hc1[0]};
-            dw_stage<2, 1>(g2, h0, stage, col, hi);
             const B2Tile gb[2] = {to_b2(g2[0]), to_b2(g2[1])};
+            dws_store(gb[0], 0, bstage, col, hi); dws_store(gb[1], 1, bstage, col, hi); dws_store(to_b2(hc1[0]), 2, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
             layer_bwd_b2<2, 2>(wbc + HC::b_off(1), PC, gb, g2b, col, hi);
-            dw_mfma_b2_col<2, 2, 0>(a_c1, stage, col, hi);
-            dw_stage_one(hc1[1], 2, stage, col, hi);
-            dw_mfma_b2_col<2, 2, 1>(a_c1, stage, col, hi);
+            dws_mfma<2, 2, 1, 0>(a_c1, bstage, col, hi);
+            dws_store(to_b2(hc1[1]), 2, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
+            dws_mfma<2, 2, 1, 1>(a_c1, bstage, col, hi);              // the two G tiles are read again, not split again
+        } else if constexpr (DWB) {
+            dws_store(to_b2(g2[0]), 0, bstage, col, hi); dws_store(to_b2(g2[1]), 1, bstage, col, hi);
+            dws_store(to_b2(hc1[0]), 2, bstage, col, hi); dws_store(to_b2(hc1[1]), 3, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
+            layer_bwd<2, 2, false>(wc + SC::lds_off(1), g2, g2b, col, hi);
+            dws_mfma<2, 2>(a_c1, bstage, col, hi);
         } else {
             dw_stage<2, 2>(g2, hc1, stage, col, hi);
             layer_bwd<2, 2, false>(wc + SC::lds_off(1), g2, g2b, col, hi);
-            dw_product<DWB, 2, 2>(a_c1, stage, col, hi);
+            dw_mfma<2, 2>(a_c1, stage, col, hi);
         }
         relu_mask(g2b[0], hc1[0]); relu_mask(g2b[1], hc1[1]);
         // color input layer
-        dw_stage<2, 1>(g2b, cin, stage, col, hi);
-        if constexpr (DXB) { const B2Tile gb[2] = {to_b2(g2b[0]), to_b2(g2b[1])}; layer_bwd_b2<2, 1>(wbc + HC::b_off(0), PC, gb, g1, col, hi); }
-        else layer_bwd<2, 1, false>(wc + SC::lds_off(0), g2b, g1, col, hi);       // g1 = dL/d(color input slots)
-        dw_product<DWB, 2, 1>(a_c0, stage, col, hi);
+        if constexpr (DWB) {
+            const B2Tile gb[2] = {to_b2(g2b[0]), to_b2(g2b[1])};
+            dws_store(gb[0], 0, bstage, col, hi); dws_store(gb[1], 1, bstage, col, hi); dws_store(to_b2(cin[0]), 2, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (DXB) layer_bwd_b2<2, 1>(wbc + HC::b_off(0), PC, gb, g1, col, hi);
+            else layer_bwd<2, 1, false>(wc + SC::lds_off(0), g2b, g1, col, hi);
+            dws_mfma<2, 1>(a_c0, bstage, col, hi);
+        } else {
+            dw_stage<2, 1>(g2b, cin, stage, col, hi);
+            layer_bwd<2, 1, false>(wc + SC::lds_off(0), g2b, g1, col, hi);        // g1 = dL/d(color input slots)
+            dw_mfma<2, 1>(a_c0, stage, col, hi);
+        }
         // slots 1..15 are density-output rows 1..15; row 0 takes dL/d(sigma raw); rows >= 16 are padding
 #pragma unroll
         for (int r = 8; r < 16; ++r) g1[0][r] = 0.f;
@@ -991,16 +1081,32 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void k_nerf_mlp_bwd_1_2(
             asm volatile("" : "+v"(sc2));                                  // a second load, not the first one kept alive
             load_enc_tile(enc_t, ld, sc2, xe[0], hi);
         }
-        dw_stage<1, 2>(g1, hd, stage, col, hi);
-        if constexpr (DXB) { const B2Tile gb[1] = {to_b2(g1[0])}; layer_bwd_b2<1, 2, 1>(wbd + HD::b_off(1), PD, gb, g2, col, hi); }
-        else layer_bwd<1, 2, false, 8>(wd + SD::lds_off(1), g1, g2, col, hi);   // 16 real output neurons
-        dw_product<DWB, 1, 2>(a_d1, stage, col, hi);
+        if constexpr (DWB) {
+            const B2Tile gb[1] = {to_b2(g1[0])};
+            dws_store(gb[0], 0, bstage, col, hi); dws_store(to_b2(hd[0]), 1, bstage, col, hi); dws_store(to_b2(hd[1]), 2, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (DXB) layer_bwd_b2<1, 2, 1>(wbd + HD::b_off(1), PD, gb, g2, col, hi);
+            else layer_bwd<1, 2, false, 8>(wd + SD::lds_off(1), g1, g2, col, hi);
+            dws_mfma<1, 2>(a_d1, bstage, col, hi);
+        } else {
+            dw_stage<1, 2>(g1, hd, stage, col, hi);
+            layer_bwd<1, 2, false, 8>(wd + SD::lds_off(1), g1, g2, col, hi);    // 16 real output neurons
+            dw_mfma<1, 2>(a_d1, stage, col, hi);
+        }
         relu_mask(g2[0], hd[0]); relu_mask(g2[1], hd[1]);
         // density input layer
-        dw_stage<2, 1>(g2, xe, stage, col, hi);
-        if constexpr (DXB) { const B2Tile gb[2] = {to_b2(g2[0]), to_b2(g2[1])}; layer_bwd_b2<2, 1>(wbd + HD::b_off(0), PD, gb, g1, col, hi); }
-        else layer_bwd<2, 1, false>(wd + SD::lds_off(0), g2, g1, col, hi);        // g1 = dL/d(encoded features)
-        dw_product<DWB, 2, 1>(a_d0, stage, col, hi);
+        if constexpr (DWB) {
+            const B2Tile gb[2] = {to_b2(g2[0]), to_b2(g2[1])};
+            dws_store(gb[0], 0, bstage, col, hi); dws_store(gb[1], 1, bstage, col, hi); dws_store(to_b2(xe[0]), 2, bstage, col, hi);
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (DXB) layer_bwd_b2<2, 1>(wbd + HD::b_off(0), PD, gb, g1, col, hi);
+            else layer_bwd<2, 1, false>(wd + SD::lds_off(0), g2, g1, col, hi);
+            dws_mfma<2, 1>(a_d0, bstage, col, hi);
+        } else {
+            dw_stage<2, 1>(g2, xe, stage, col, hi);
+            layer_bwd<2, 1, false>(wd + SD::lds_off(0), g2, g1, col, hi);         // g1 = dL/d(encoded features)
+            dw_mfma<2, 1>(a_d0, stage, col, hi);
+        }
         if (live) {
             store_enc_tile(denc_t, ld, s, g1[0], hi);
         }
@@ -2551,7 +2657,8 @@ static int mlp_bwd_f32(const float* enc_t, uint32_t ld, const float* dirs, uint3
     constexpr size_t bt2 = (size_t)2 * (HShape<1>::b_halves + HShape<2>::b_halves) * sizeof(__bf16);
     constexpr size_t ft2 = (size_t)2 * (F2Shape<1>::halves + F2Shape<2>::halves) * sizeof(__bf16);
     constexpr size_t w32 = (NetShape<1>::lds_floats + NetShape<2>::lds_floats) * sizeof(float);
-    constexpr size_t st3 = (size_t)MLP_WAVES * 3 * 32 * ST33 * sizeof(float);
+    constexpr size_t st3 = (size_t)MLP_WAVES * 3 * DWS_TILE * sizeof(__bf16);       // the 16-bit dW stage of the kernel's DWB modes
+    if (mode == 1) lds = w32 + (size_t)MLP_WAVES * 4 * DWS_TILE * sizeof(__bf16);
     if (mode == 2) lds = w32 + bt2 + st3;
     if (mode >= 3) lds = ft2 + bt2 + st3;
     if (mlp_set_lds((const void*)kern, lds) != XR_OK) { xr_set_error("hipFuncSetAttribute failed"); return XR_EHIP; }
