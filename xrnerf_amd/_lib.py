@@ -173,6 +173,14 @@ BUNGEE_SIGNATURES = {
     'xr_bungee_render_backward': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _i32, _f, _f, _i32, _i32, _vp, _vp]),
 }
 
+# Vanilla NeRF (csrc/xr_vanilla.hip, declared in include/xrnerf_mi355_vanilla.h): a table of its own for the same reason
+VANILLA_SIGNATURES = {
+    'xr_nerf_encode': (_i32, [_vp, _vp, _u64, _u32, _i32, _i32, _vp, _u32, _vp]),
+    'xr_nerf_render_train_forward': (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'xr_nerf_render_backward': (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
+    'xr_nerf_sample_pdf': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -228,7 +236,7 @@ def load():
                 finally:
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

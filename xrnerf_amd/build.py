@@ -34,6 +34,8 @@ SOURCES = {
     'xr_kilo.hip': ['-ffp-contract=off'],
     # BungeeNeRF stages: fp32 in the reference's operation order, like xr_mip.hip
     'xr_bungee.hip': ['-ffp-contract=off'],
+    # vanilla-NeRF stages (encode, training renderer, sample_pdf): fp32 in the reference's operation order as well
+    'xr_vanilla.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],
@@ -54,7 +56,7 @@ def sources_hash():
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')))
     for f in files + [os.path.join(HERE, '..', 'include', 'xrnerf_mi355.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'),
-                      os.path.abspath(__file__)]:
+                      os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'), os.path.abspath(__file__)]:
         h.update(os.path.basename(f).encode() + b'\0')
         with open(f, 'rb') as fh:
             h.update(fh.read())
@@ -81,7 +83,7 @@ def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, 'xr_common.h'), os.path.join(CSRC, 'xr_mip_math.h'), os.path.join(CSRC, 'xr_hashgrid.h'),
                os.path.join(CSRC, 'xr_scatter.h'), os.path.join(CSRC, 'xr_adam.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355.h'),
-               os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'),
+               os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'),
                os.path.abspath(__file__)]
     have_src = all(os.path.exists(os.path.join(CSRC, s)) for s in SOURCES)
     if not have_src:

@@ -1562,3 +1562,98 @@ def bungee_render_backward(raw, z_vals, viewdirs, grad_rgb, stage, density_bias=
                                                          int(bool(white_bkgd)), _MIP_ACT[density_activation], _ptr(out), _stream()),
                    'xr_bungee_render_backward')
     return out
+
+
+# ---------------------------------------------------------------- vanilla NeRF (configs/nerf/nerf_blender_base01.py)
+def vanilla_kernels_available():
+    """the loaded library handle has xr_vanilla.hip's entry points.  libxrnerf_mi355.so always has (load() fails otherwise); a handle
+    made of the host builds of other sources (tests/hip_emu) may not, and the modules of vanilla.py then keep their tensor-op path"""
+    return hasattr(_lib.load(), 'xr_nerf_encode')
+
+
+def nerf_encode_channels(multires, multires_dirs):
+    return 6 + 6 * int(multires) + 6 * int(multires_dirs)
+
+
+def nerf_encode(pts, viewdirs, multires, multires_dirs, out=None):
+    """BaseEmbedder.forward in one launch: pts [..., 3] (n_rows points), viewdirs [n_dirs, 3] with n_rows a multiple of n_dirs (row r
+    takes direction r // (n_rows / n_dirs)) -> [n_rows, channels]: a column range of a buffer whose rows are padded to a multiple of
+    4 floats (padding written as zeros), which the linear kernels read in place"""
+    pts, viewdirs = _f32c(pts).reshape(-1, 3), _f32c(viewdirs).reshape(-1, 3)
+    n, nd = pts.shape[0], viewdirs.shape[0]
+    if n and (nd == 0 or n % nd):
+        raise _lib.XrError('nerf_encode: %d points cannot share %d directions evenly' % (n, nd))
+    ch = nerf_encode_channels(multires, multires_dirs)
+    if out is None:
+        out = torch.empty((n, (ch + 3) // 4 * 4), dtype=torch.float32, device=pts.device)
+    if (not _on_device(out) or out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != n
+            or out.stride(0) < (ch + 3) // 4 * 4):
+        raise _lib.XrError('nerf_encode: out must be a float32 device matrix of %d rows with a row stride of >= %d floats' % (n, (ch + 3) // 4 * 4))
+    _ptr(viewdirs)                                                     # (host tensors are refused here)
+    with _span('xr_nerf_encode', n):
+        _lib.check(_lib.load().xr_nerf_encode(_ptr(pts), _ptr(viewdirs), n, n // nd if n else 1, int(multires), int(multires_dirs),
+                                              C.c_void_p(out.data_ptr()), out.stride(0), _stream()), 'xr_nerf_encode')
+    return out[:, :ch]
+
+
+def _nerf_render_common(raw, z_vals, rays_d, noise):
+    raw, z_vals, rays_d = _f32c(raw), _f32c(z_vals), _f32c(rays_d)
+    R, S = z_vals.shape
+    if tuple(raw.shape) != (R, S, 4) or tuple(rays_d.shape) != (R, 3):
+        raise _lib.XrError('the NeRF renderer takes raw [R, S, 4], z_vals [R, S] and rays_d [R, 3]')
+    if noise is not None:
+        noise = _f32c(noise)
+        if tuple(noise.shape) != (R, S):
+            raise _lib.XrError('noise must be [R, S]')
+    return raw, z_vals, rays_d, noise, R, S
+
+
+def nerf_render_train_forward(raw, z_vals, rays_d, white_bkgd, noise=None):
+    """NerfRender.forward (relu density, no padding, no bias) with the optional density noise: -> rgb [R,3], disp [R], acc [R], weights [R,S]"""
+    raw, z_vals, rays_d, noise, R, S = _nerf_render_common(raw, z_vals, rays_d, noise)
+    dev = raw.device
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    disp = torch.empty((R,), dtype=torch.float32, device=dev)
+    acc = torch.empty((R,), dtype=torch.float32, device=dev)
+    w = torch.empty((R, S), dtype=torch.float32, device=dev)
+    with _span('xr_nerf_render_train_forward', R * S):
+        _lib.check(_lib.load().xr_nerf_render_train_forward(_ptr(raw), _ptr(z_vals), _ptr(rays_d), _ptr(noise), R, S, int(bool(white_bkgd)),
+                                                            _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(w), _stream()),
+                   'xr_nerf_render_train_forward')
+    return rgb, disp, acc, w
+
+
+def nerf_render_backward(raw, z_vals, rays_d, grad_rgb, white_bkgd, noise=None):
+    """dL/draw [R,S,4] given dL/drgb [R,3] (recomputed from the forward's inputs)"""
+    raw, z_vals, rays_d, noise, R, S = _nerf_render_common(raw, z_vals, rays_d, noise)
+    grad_rgb = _f32c(grad_rgb)
+    if tuple(grad_rgb.shape) != (R, 3):
+        raise _lib.XrError('grad_rgb must be [R, 3]')
+    out = torch.empty_like(raw)
+    with _span('xr_nerf_render_backward', R * S):
+        _lib.check(_lib.load().xr_nerf_render_backward(_ptr(raw), _ptr(z_vals), _ptr(rays_d), _ptr(noise), R, S, int(bool(white_bkgd)),
+                                                       _ptr(grad_rgb), _ptr(out), _stream()), 'xr_nerf_render_backward')
+    return out
+
+
+def nerf_sample_pdf(z_vals, weights, rays_o, rays_d, n_new, u=None, want_samples=False):
+    """sample_pdf + the merge with the coarse samples + GetPts in one launch: -> (z_all [R, S+n_new], pts [R, S+n_new, 3]) and, with
+    want_samples, the new samples [R, n_new] before the merge.  u [R, n_new]: the uniform draws; None = linspace(0, 1, n_new)."""
+    z_vals, weights = _f32c(z_vals), _f32c(weights.detach())
+    rays_o, rays_d = _f32c(rays_o), _f32c(rays_d)
+    R, S = z_vals.shape
+    N = int(n_new)
+    if tuple(weights.shape) != (R, S) or tuple(rays_o.shape) != (R, 3) or tuple(rays_d.shape) != (R, 3):
+        raise _lib.XrError('nerf_sample_pdf takes z_vals / weights [R, S] and rays_o / rays_d [R, 3]')
+    if u is not None:
+        u = _f32c(u)
+        if tuple(u.shape) != (R, N):
+            raise _lib.XrError('u must be [R, n_new]')
+    dev = z_vals.device
+    z_all = torch.empty((R, S + max(N, 0)), dtype=torch.float32, device=dev)
+    pts = torch.empty((R, S + max(N, 0), 3), dtype=torch.float32, device=dev)
+    zs = torch.empty((R, max(N, 0)), dtype=torch.float32, device=dev) if want_samples else None
+    with _span('xr_nerf_sample_pdf', R):
+        _lib.check(_lib.load().xr_nerf_sample_pdf(_ptr(z_vals), _ptr(weights), _ptr(u), _ptr(rays_o), _ptr(rays_d), R, S, max(N, 0),
+                                                  _ptr(z_all), _ptr(pts), _ptr(zs), _stream()), 'xr_nerf_sample_pdf')
+    return (z_all, pts, zs) if want_samples else (z_all, pts)

@@ -2,8 +2,10 @@
 `NerfNetwork`, `NerfMLP`, `BaseEmbedder`, `NerfRender`, plus stratified / hierarchical sampling.
 
 This is the reference's only renderer that runs on a CPU as shipped and is
-pure PyTorch there as well; it is plumbing for the registry contract and the CPU-runnable parity
-case, not a hot path: plain tensor code, no kernels.  Constructor signatures, `data` dict keys,
+pure PyTorch there.  Host tensors take plain tensor code (the CPU-runnable parity case).  On the device a training step is
+  encode (xr_nerf_encode) -> the MLP as ONE autograd node over the linear kernels (_NerfMlpFn) -> renderer forward / backward
+  (xr_nerf_render_train_forward / xr_nerf_render_backward, _NerfRenderFn) -> resampling + merge + points (xr_nerf_sample_pdf)
+and the same again for the fine network (xrnerf_amd/csrc/xr_vanilla.hip; DESIGN.md "Vanilla NeRF (config #1)").  Constructor signatures, `data` dict keys,
 sub-module / parameter names (`pts_linears.N`, `views_linears.0`, `feature_linear`, `alpha_linear`,
 `rgb_linear`) and numerics follow
   /root/reference/xrnerf/models/embedders/base.py:8-77, mlps/nerf_mlp.py:11-94,
@@ -31,6 +33,7 @@ class BaseEmbedder(nn.Module):
             self.freqs, self.freqs_dirs = None, None
             self.embed_ch = self.embed_ch_dirs = input_ch
         else:
+            self.multires, self.multires_dirs = int(multires), int(multires_dirs)
             self.freqs = [float(2.0 ** k) for k in range(multires)]          # 2**linspace(0, L-1, L)
             self.freqs_dirs = [float(2.0 ** k) for k in range(multires_dirs)]
             self.embed_ch = input_ch * (1 + 2 * multires)
@@ -49,9 +52,28 @@ class BaseEmbedder(nn.Module):
             parts.append(torch.cos(x * f))
         return torch.cat(parts, -1)
 
+    def _kernel_ok(self, pts, viewdirs):
+        from . import ops
+        if self.freqs is None or self.input_ch != 3 or self.multires > 16 or self.multires_dirs > 16:
+            return False
+        if not (ops._on_device(pts) and ops._on_device(viewdirs) and pts.dtype == viewdirs.dtype == torch.float32):
+            return False
+        if pts.shape[-1] != 3 or viewdirs.shape[-1] != 3 or pts.numel() == 0:
+            return False
+        if torch.is_grad_enabled() and (pts.requires_grad or viewdirs.requires_grad):
+            return False                              # the kernel has no backward: a differentiable input keeps the tensor ops
+        # [R, S, 3] points with one direction per ray, or one direction per point
+        shared = pts.dim() == viewdirs.dim() + 1 and pts.shape[:-2] == viewdirs.shape[:-1]
+        return (shared or pts.shape == viewdirs.shape) and ops.vanilla_kernels_available()
+
     def forward(self, data):
         pts, viewdirs = data['pts'], data['viewdirs']
         data['unflatten_shape'] = pts.shape[:-1]
+        if self._kernel_ok(pts, viewdirs):
+            # device: one launch; rows padded to a multiple of 4 floats (zeros), which NerfMLP's linear kernels read in place
+            from . import ops
+            data['embedded'] = ops.nerf_encode(pts, viewdirs, self.multires, self.multires_dirs)
+            return data
         if pts.dim() > viewdirs.dim():
             viewdirs = viewdirs[:, None].expand(pts.shape)
         e_pts = self.run_embed(pts.reshape(-1, pts.shape[-1]), self.freqs)
@@ -87,9 +109,18 @@ class NerfMLP(nn.Module):
     def _device_graph_ok(self, x):
         W = self.pts_linears[0].weight.shape[0]
         from . import ops
-        return (ops._on_device(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 and self.use_viewdirs and len(self.views_linears) == 1
-                and self.input_ch % 4 == 0 and W % 4 == 0 and (W // 2) % 4 == 0 and (len(self.pts_linears) - 1) not in self.skips
-                and all(l.weight.shape[0] == W for l in self.pts_linears))
+        if not (ops._on_device(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 and self.use_viewdirs and len(self.views_linears) == 1
+                and W % 4 == 0 and (W // 2) % 4 == 0 and (len(self.pts_linears) - 1) not in self.skips
+                and all(l.weight.shape[0] == W for l in self.pts_linears)):
+            return False
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False                                  # the node has no input gradient: the per-layer graph provides it
+        if any(p.dtype != torch.float32 or p.device != x.device for p in self.parameters()):
+            return False
+        if self.input_ch % 4:
+            # the first trunk layer and the skip buffer read ceil4(input_ch) columns of x in place (part of the vanilla-NeRF device path)
+            return x.shape[1] >= (self.input_ch + 3) // 4 * 4 and ops.vanilla_kernels_available()
+        return True
 
     def run_mlp(self, x):
         if self._device_graph_ok(x):
@@ -167,18 +198,31 @@ class _NerfMlpFn(torch.autograd.Function):
         pts = [p.detach() for p in params[:2 * D]]
         xr, _ = ops._rows(x.detach())
         M, W, W2 = xr.shape[0], pts[0].shape[0], vw.shape[0]
-        x_pts, x_dir = xr[:, :ic], xr[:, ic:ic + idr]
+        # input_ch not a multiple of 4 (63 in config #1): the trunk reads Kx = ceil4(input_ch) columns of x in place and the weights get
+        # zero columns there (the columns hold finite values -- the first direction features or the encoder's zero padding: w * x = 0 exactly)
+        Kx = (ic + 3) // 4 * 4
+        if xr.shape[1] < Kx or xr.shape[1] < ic + idr:
+            raise ops._lib.XrError('NerfMLP: the embedding has %d columns, expected %d' % (xr.shape[1], ic + idr))
+        x_pts, x_dir = xr[:, :Kx], xr[:, ic:ic + idr]
+        wts = [pts[2 * i] for i in range(D)]
+        if Kx != ic:
+            for i in range(D):
+                if i == 0 or (i - 1) in skips:
+                    wp = wts[i].new_zeros((W, wts[i].shape[1] + Kx - ic))
+                    wp[:, :ic] = wts[i][:, :ic]
+                    wp[:, Kx:] = wts[i][:, ic:]
+                    wts[i] = wp
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=xr.device)
         acts, h = [], x_pts
         for i in range(D):
             if i in skips:
-                cat = new(M, ic + W)
-                cat[:, :ic].copy_(x_pts)
-                y = ops.linear_forward(h, pts[2 * i], pts[2 * i + 1], True, out=cat[:, ic:])
+                cat = new(M, Kx + W)
+                cat[:, :Kx].copy_(x_pts)
+                y = ops.linear_forward(h, wts[i], pts[2 * i + 1], True, out=cat[:, Kx:])
                 acts.append((h, y))
                 h = cat
             else:
-                y = ops.linear_forward(h, pts[2 * i], pts[2 * i + 1], True)
+                y = ops.linear_forward(h, wts[i], pts[2 * i + 1], True)
                 acts.append((h, y))
                 h = y
         o_dir = W + 4
@@ -198,16 +242,19 @@ class _NerfMlpFn(torch.autograd.Function):
         br2 = torch.cat([rb, rb.new_zeros((1,))], 0)
         raw = ops.linear_forward(hv, wr2, br2, False)
         raw[:, 3].copy_(V[:, W])
-        ctx.cfg = (tuple(skips), ic, idr, D, W, W2, o_dir, KV)
+        ctx.cfg = (tuple(skips), ic, idr, D, W, W2, o_dir, KV, Kx)
         ctx.acts, ctx.h_last, ctx.V, ctx.hv = acts, h, V, hv
-        ctx.w = (pts, wb, wv2, wr2)
+        ctx.w = (wts, wb, wv2, wr2)
         return raw
 
     @staticmethod
     def backward(ctx, d_raw):
         from . import ops
-        skips, ic, idr, D, W, W2, o_dir, KV = ctx.cfg
-        pts, wb, wv2, wr2 = ctx.w
+        if ctx.needs_input_grad[0]:
+            raise ops._lib.XrError('_NerfMlpFn has no gradient with respect to its input: NerfMLP.run_mlp takes the per-layer graph for '
+                                   'an input that requires one')
+        skips, ic, idr, D, W, W2, o_dir, KV, Kx = ctx.cfg
+        wts, wb, wv2, wr2 = ctx.w
         acts, V, hv = ctx.acts, ctx.V, ctx.hv
         d_raw = d_raw.contiguous()
         dwr2, dbr2 = ops.linear_backward_weight_bias(d_raw, None, hv)
@@ -221,16 +268,40 @@ class _NerfMlpFn(torch.autograd.Function):
         grads = [None] * (2 * D)
         for i in range(D - 1, -1, -1):
             xin, y = acts[i]
-            dy = dh[:, ic:] if i in skips else dh
-            grads[2 * i], grads[2 * i + 1] = ops.linear_backward_weight_bias(dy, y, xin)
+            dy = dh[:, Kx:] if i in skips else dh
+            dw, grads[2 * i + 1] = ops.linear_backward_weight_bias(dy, y, xin)
+            if Kx != ic and (i == 0 or (i - 1) in skips):
+                dw = torch.cat([dw[:, :ic], dw[:, Kx:]], 1)            # without the zero columns of the padded weight
+            grads[2 * i] = dw
             if i > 0:
-                dh = ops.linear_backward_input(dy, y, pts[2 * i])
+                dh = ops.linear_backward_input(dy, y, wts[i])
         dvw = torch.cat([dwv2[:, :W], dwv2[:, o_dir:o_dir + idr]], 1)
         ctx.acts = ctx.h_last = ctx.V = ctx.hv = None
         return (None, None, None, None) + tuple(grads) + (dvw, dbv, dwb[:W], dbb[:W], dwb[W:W + 1], dbb[W:W + 1], dwr2[:3], dbr2[:3])
 
 
 # ------------------------------------------------------------------ classic volume rendering
+class _NerfRenderFn(torch.autograd.Function):
+    """NerfRender.forward for training as one launch forward and one backward (xr_nerf_render_train_forward / xr_nerf_render_backward).
+    Gradients flow from the colours only -- all the reference's loss reads (networks/nerf.py:71-92); disp, acc and the weights (which
+    feed the detached resampler) are marked non-differentiable rather than silently given a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, raw, z_vals, rays_d, noise, white_bkgd):
+        from . import ops
+        rgb, disp, acc, w = ops.nerf_render_train_forward(raw, z_vals, rays_d, white_bkgd, noise)
+        ctx.save_for_backward(raw, z_vals, rays_d, noise)
+        ctx.white_bkgd = white_bkgd
+        ctx.mark_non_differentiable(disp, acc, w)
+        return rgb, disp, acc, w
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_acc, g_w):
+        from . import ops
+        raw, z_vals, rays_d, noise = ctx.saved_tensors
+        return ops.nerf_render_backward(raw, z_vals, rays_d, g_rgb, ctx.white_bkgd, noise), None, None, None, None
+
+
 @RENDERS.register_module()
 class NerfRender(nn.Module):
     def __init__(self, white_bkgd=False, raw_noise_std=0, rgb_padding=0, density_bias=0, density_activation='relu',
@@ -261,11 +332,21 @@ class NerfRender(nn.Module):
     def forward(self, data, is_test=False):
         raw, z_vals, rays_d = data['raw'], data['z_vals'], data['rays_d']
         noise_std = 0 if is_test else self.raw_noise_std
+        from . import ops
+        if (torch.is_grad_enabled() and raw.requires_grad and ops._on_device(raw) and raw.dtype == torch.float32
+                and self.density_activation is F.relu and self.rgb_padding == 0 and self.density_bias == 0
+                and raw.dim() == 3 and raw.shape[-1] == 4 and raw.shape[0] > 0 and 1 <= raw.shape[1] <= 4096
+                and tuple(z_vals.shape) == tuple(raw.shape[:2]) and tuple(rays_d.shape) == (raw.shape[0], 3)
+                and not z_vals.requires_grad and not rays_d.requires_grad and ops.vanilla_kernels_available()):
+            # training on the device: one launch forward, one backward (_NerfRenderFn); gradients flow from the colours
+            noise = torch.randn(raw.shape[:2], device=raw.device) * noise_std if noise_std > 0. else None
+            rgb_map, disp, acc, weights = _NerfRenderFn.apply(raw, z_vals, rays_d, noise, bool(self.white_bkgd))
+            data['weights'] = weights
+            return data, {'rgb': rgb_map, 'disp': disp, 'acc': acc}
         if (raw.is_cuda and not (torch.is_grad_enabled() and raw.requires_grad) and noise_std == 0
                 and self.density_activation is F.relu and self.rgb_padding == 0 and self.density_bias == 0
                 and raw.dim() == 3 and raw.shape[-1] == 4 and tuple(z_vals.shape) == tuple(raw.shape[:2])):
             # inference on the device: one launch (xr_nerf_render_forward) instead of ~25 tensor ops
-            from . import ops
             rgb_map, disp, acc, weights = ops.nerf_render_forward(raw, z_vals, rays_d, self.white_bkgd)
             data['weights'] = weights
             return data, {'rgb': rgb_map, 'disp': disp, 'acc': acc}
@@ -313,8 +394,19 @@ def get_pts(rays_o, rays_d, z_vals):
 def sample_pdf(data, N_samples, is_perturb=False, is_test=False, u=None):
     """hierarchical re-sampling from the coarse weights (networks/utils/hierarchical_sample.py:6-53)"""
     z_vals, rays_o, rays_d = data['z_vals'], data['rays_o'], data['rays_d']
-    weights = data['weights'][..., 1:-1] + 1e-5
     det = True if is_test else (not is_perturb)
+    from . import ops
+    if (ops._on_device(z_vals) and z_vals.dtype == torch.float32 and z_vals.dim() == 2 and z_vals.shape[0] > 0 and 3 <= z_vals.shape[1] <= 1024
+            and 1 <= N_samples <= 1024 and data['weights'].shape == z_vals.shape and tuple(rays_o.shape) == (z_vals.shape[0], 3)
+            and rays_d.shape == rays_o.shape and ops.vanilla_kernels_available()):
+        # device: inversion, merge, sort and the new points in one launch; the draws are made on the device (no host draw, no copy)
+        if u is None and not det:
+            u = torch.rand((z_vals.shape[0], N_samples), device=z_vals.device)
+        elif u is not None:
+            u = u.to(z_vals.device).expand(z_vals.shape[0], N_samples)
+        data['z_vals'], data['pts'] = ops.nerf_sample_pdf(z_vals, data['weights'], rays_o, rays_d, N_samples, u)
+        return data
+    weights = data['weights'][..., 1:-1] + 1e-5
     bins = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
     pdf = weights / torch.sum(weights, -1, keepdim=True)
     cdf = torch.cumsum(pdf, -1)
