@@ -181,6 +181,18 @@ VANILLA_SIGNATURES = {
     'xr_nerf_sample_pdf': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
 }
 
+# Animatable NeRF (csrc/xr_aninerf.hip, declared in include/xrnerf_mi355_aninerf.h): a table of its own as well
+ANINERF_SIGNATURES = {
+    'xr_ani_closest': (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xr_ani_select_workspace_bytes': (_sz, [_u32]),
+    'xr_ani_select': (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
+    'xr_ani_blend_forward': (_i32, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    'xr_ani_blend_backward': (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    'xr_ani_skin_forward': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    'xr_ani_skin_backward': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    'xr_ani_encode_backward': (_i32, [_vp, _vp, _u32, _u32, _i32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -236,7 +248,8 @@ def load():
                 finally:
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
+            list(ANINERF_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -36,6 +36,9 @@ SOURCES = {
     'xr_bungee.hip': ['-ffp-contract=off'],
     # vanilla-NeRF stages (encode, training renderer, sample_pdf): fp32 in the reference's operation order as well
     'xr_vanilla.hip': ['-ffp-contract=off'],
+    # Animatable-NeRF stages (closest vertex, selection, blend head, skinning, encode backward): the nearest-vertex decision is made on
+    # d2 = (dx dx + dy dy) + dz dz, which must round like its fp32 tensor-op restatement
+    'xr_aninerf.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],
@@ -56,7 +59,8 @@ def sources_hash():
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')))
     for f in files + [os.path.join(HERE, '..', 'include', 'xrnerf_mi355.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'),
-                      os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'), os.path.abspath(__file__)]:
+                      os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'),
+                      os.path.join(HERE, '..', 'include', 'xrnerf_mi355_aninerf.h'), os.path.abspath(__file__)]:
         h.update(os.path.basename(f).encode() + b'\0')
         with open(f, 'rb') as fh:
             h.update(fh.read())
@@ -84,7 +88,7 @@ def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, 'xr_common.h'), os.path.join(CSRC, 'xr_mip_math.h'), os.path.join(CSRC, 'xr_hashgrid.h'),
                os.path.join(CSRC, 'xr_scatter.h'), os.path.join(CSRC, 'xr_adam.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355.h'),
                os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'),
-               os.path.abspath(__file__)]
+               os.path.join(HERE, '..', 'include', 'xrnerf_mi355_aninerf.h'), os.path.abspath(__file__)]
     have_src = all(os.path.exists(os.path.join(CSRC, s)) for s in SOURCES)
     if not have_src:
         if os.path.exists(OUT):

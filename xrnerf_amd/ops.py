@@ -1657,3 +1657,160 @@ def nerf_sample_pdf(z_vals, weights, rays_o, rays_d, n_new, u=None, want_samples
         _lib.check(_lib.load().xr_nerf_sample_pdf(_ptr(z_vals), _ptr(weights), _ptr(u), _ptr(rays_o), _ptr(rays_d), R, S, max(N, 0),
                                                   _ptr(z_all), _ptr(pts), _ptr(zs), _stream()), 'xr_nerf_sample_pdf')
     return (z_all, pts, zs) if want_samples else (z_all, pts)
+
+
+# ---------------------------------------------------------------- Animatable NeRF (configs/animatable_nerf/an_h36m_s9_train_pose.py)
+ANI_JOINTS = 24                 # XR_ANI_JOINTS
+ANI_CLOSEST_TILE = 1024         # XR_ANI_CLOSEST_TILE: vertices staged in LDS at a time
+
+
+def aninerf_kernels_available():
+    """the loaded library handle has xr_aninerf.hip's entry points.  libxrnerf_mi355.so always has (load() fails otherwise); a handle
+    made of the host builds of other sources (tests/hip_emu) may not, and the modules of aninerf.py then keep their tensor-op path"""
+    return hasattr(_lib.load(), 'xr_ani_closest')
+
+
+def _i32c(t):
+    if t.dtype != torch.int32:
+        raise _lib.XrError('expected an int32 tensor (got %s)' % t.dtype)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def ani_closest(pts, verts, th, R=None, T=None, want_d2=False):
+    """nearest vertex of every point (knn_points with K = 1), after the optional world -> pose transform (p - T) R of points AND vertices:
+    pts [N,3], verts [V,3] -> (q [N,3] the transformed points, idx [N] int32, dist [N], flag [N] int32 = dist < th) and, with want_d2,
+    the squared distances [N]"""
+    pts, verts = _f32c(pts).reshape(-1, 3), _f32c(verts).reshape(-1, 3)
+    if (R is None) != (T is None):
+        raise _lib.XrError('ani_closest: R and T come together')
+    if R is not None:
+        R, T = _f32c(R).reshape(3, 3), _f32c(T).reshape(3)
+    N, V = pts.shape[0], verts.shape[0]
+    dev = pts.device
+    q = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((N,), dtype=torch.int32, device=dev)
+    dist = torch.empty((N,), dtype=torch.float32, device=dev)
+    flag = torch.empty((N,), dtype=torch.int32, device=dev)
+    d2 = torch.empty((N,), dtype=torch.float32, device=dev) if want_d2 else None
+    _ptr(verts)                                                        # (host tensors are refused here, N = 0 included)
+    with _span('xr_ani_closest', N):
+        _lib.check(_lib.load().xr_ani_closest(_ptr(pts), _ptr(verts), _ptr(R), _ptr(T), N, V, float(th), _ptr(q), _ptr(idx), _ptr(d2),
+                                              _ptr(dist), _ptr(flag), _stream()), 'xr_ani_closest')
+    return (q, idx, dist, flag, d2) if want_d2 else (q, idx, dist, flag)
+
+
+def ani_select(flag, dist):
+    """pind = flag; pind[argmin(dist)] = True; -> (list [N] int32 whose first `count` entries are nonzero(pind) in ascending order,
+    count [1] int32), both on the device: the caller reads the count once"""
+    flag, dist = _i32c(flag).reshape(-1), _f32c(dist).reshape(-1)
+    N = flag.shape[0]
+    if dist.shape[0] != N:
+        raise _lib.XrError('ani_select: flag and dist differ in length')
+    dev = flag.device
+    lst = torch.empty((N,), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = int(lib.xr_ani_select_workspace_bytes(N))
+    ws = _ws(dev, nbytes, 'ani_select')
+    _ptr(dist)
+    with _span('xr_ani_select', N):
+        _lib.check(lib.xr_ani_select(_ptr(flag), _ptr(dist), N, _ptr(lst), _ptr(count), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+                   'xr_ani_select')
+    return lst, count
+
+
+def _bw_rows(t, what):
+    t = _f32c(t)
+    if t.dim() != 2 or t.shape[1] != ANI_JOINTS:
+        raise _lib.XrError('%s must be [N, %d]' % (what, ANI_JOINTS))
+    return t
+
+
+def ani_blend_forward(smpl_bw, idx, logits):
+    """softmax_j(log(smpl_bw[idx, j] + 1e-9) + logits[:, j]) -> [N,24]"""
+    smpl_bw, logits, idx = _bw_rows(smpl_bw, 'smpl_bw'), _bw_rows(logits, 'logits'), _i32c(idx).reshape(-1)
+    N = logits.shape[0]
+    if idx.shape[0] != N:
+        raise _lib.XrError('ani_blend_forward: idx and logits differ in length')
+    out = torch.empty_like(logits)
+    _ptr(smpl_bw)
+    with _span('xr_ani_blend_forward', N):
+        _lib.check(_lib.load().xr_ani_blend_forward(_ptr(smpl_bw), _ptr(idx), _ptr(logits), N, _ptr(out), _stream()), 'xr_ani_blend_forward')
+    return out
+
+
+def ani_blend_backward(bw, grad_bw):
+    """dL/dlogits [N,24] from the head's output and dL/dbw"""
+    bw, grad_bw = _bw_rows(bw, 'bw'), _bw_rows(grad_bw, 'grad_bw')
+    if grad_bw.shape != bw.shape:
+        raise _lib.XrError('ani_blend_backward: bw and grad_bw differ in shape')
+    out = torch.empty_like(bw)
+    _ptr(grad_bw)
+    with _span('xr_ani_blend_backward', bw.shape[0]):
+        _lib.check(_lib.load().xr_ani_blend_backward(_ptr(bw), _ptr(grad_bw), bw.shape[0], _ptr(out), _stream()), 'xr_ani_blend_backward')
+    return out
+
+
+def _skin_common(pts, dirs, bw, a_from, a_to):
+    pts, bw = _f32c(pts).reshape(-1, 3), _bw_rows(bw, 'bw')
+    a_from, a_to = _f32c(a_from).reshape(-1, 16), _f32c(a_to).reshape(-1, 16)
+    N = pts.shape[0]
+    if bw.shape[0] != N or a_from.shape[0] != ANI_JOINTS or a_to.shape[0] != ANI_JOINTS:
+        raise _lib.XrError('skinning takes pts [N,3], bw [N,24] and two sets of 24 4x4 matrices')
+    if dirs is not None:
+        dirs = _f32c(dirs).reshape(-1, 3)
+        if dirs.shape[0] != N:
+            raise _lib.XrError('dirs must be [N,3]')
+    return pts, dirs, bw, a_from, a_to, N
+
+
+def ani_skin_forward(pts, dirs, bw, a_from, a_to):
+    """p'' = B_R A_R^-1 (p - A_t) + B_t and d'' = B_R A_R^-1 d with A = sum_j bw_j a_from[j], B = sum_j bw_j a_to[j]
+    -> (pts_out [N,3], dirs_out [N,3] or None)"""
+    pts, dirs, bw, a_from, a_to, N = _skin_common(pts, dirs, bw, a_from, a_to)
+    po = torch.empty_like(pts)
+    do = torch.empty_like(dirs) if dirs is not None else None
+    _ptr(a_from)
+    with _span('xr_ani_skin_forward', N):
+        _lib.check(_lib.load().xr_ani_skin_forward(_ptr(pts), _ptr(dirs), _ptr(bw), _ptr(a_from), _ptr(a_to), N, _ptr(po), _ptr(do), _stream()),
+                   'xr_ani_skin_forward')
+    return po, do
+
+
+def ani_skin_backward(pts, dirs, bw, a_from, a_to, grad_pts, grad_dirs=None):
+    """dL/dbw [N,24] from dL/dp'' and dL/dd'' (either may be None), recomputed from the forward's inputs"""
+    pts, dirs, bw, a_from, a_to, N = _skin_common(pts, dirs, bw, a_from, a_to)
+    if grad_pts is not None:
+        grad_pts = _f32c(grad_pts).reshape(-1, 3)
+    if grad_dirs is not None:
+        grad_dirs = _f32c(grad_dirs).reshape(-1, 3)
+    for g in (grad_pts, grad_dirs):
+        if g is not None and g.shape[0] != N:
+            raise _lib.XrError('the skinning gradients must be [N,3]')
+    if grad_dirs is not None and dirs is None:
+        raise _lib.XrError('grad_dirs given without dirs')
+    out = torch.empty_like(bw)
+    _ptr(a_from)
+    with _span('xr_ani_skin_backward', N):
+        _lib.check(_lib.load().xr_ani_skin_backward(_ptr(pts), _ptr(dirs), _ptr(bw), _ptr(a_from), _ptr(a_to), N, _ptr(grad_pts),
+                                                    _ptr(grad_dirs), _ptr(out), _stream()), 'xr_ani_skin_backward')
+    return out
+
+
+def ani_encode_backward(pts, grad, multires):
+    """input gradient of BaseEmbedder's point encoding: pts [N,3], grad [N, >= 3 + 6 multires] (a column range of a wider matrix is
+    read in place, at its row stride) -> dL/dpts [N,3]"""
+    pts = _f32c(pts).reshape(-1, 3)
+    N, cp = pts.shape[0], 3 + 6 * int(multires)
+    if grad.dtype != torch.float32 or grad.dim() != 2 or grad.shape[0] != N or grad.shape[1] < cp:
+        raise _lib.XrError('ani_encode_backward: grad must be float32 [N, >= %d]' % cp)
+    if N and (grad.stride(1) != 1 or grad.stride(0) < cp):
+        grad = grad.contiguous()
+    if not _on_device(grad):
+        _ptr(grad)
+    out = torch.empty_like(pts)
+    _ptr(pts)
+    with _span('xr_ani_encode_backward', N):
+        _lib.check(_lib.load().xr_ani_encode_backward(_ptr(pts), C.c_void_p(grad.data_ptr()), grad.stride(0) if N else cp, N, int(multires),
+                                                      _ptr(out), _stream()), 'xr_ani_encode_backward')
+    return out
