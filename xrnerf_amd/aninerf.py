@@ -181,22 +181,12 @@ def embed(p, L):
 
 
 def _lin(x, w, b, relu=False):
-    """act(x w^T + b): the linear kernels on the device (K and N brought to multiples of 4 with zeros), torch on the host"""
-    from . import ops
-    if _TENSOR_OPS or not (ops._on_device(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0):
+    """act(x w^T + b): the linear kernels on the device (linear.linear_act_padded), torch on the host or with the tensor-op switch"""
+    if _TENSOR_OPS:
         y = F.linear(x, w, b)
         return F.relu(y) if relu else y
-    from .linear import linear_act
-    N, K = w.shape
-    pk, pn = (-K) % 4, (-N) % 4
-    if pk:
-        x = torch.cat([x, x.new_zeros((x.shape[0], pk))], -1)
-        w = F.pad(w, (0, pk))
-    if pn:
-        w = F.pad(w, (0, 0, 0, pn))
-        b = F.pad(b, (0, pn)) if b is not None else None
-    y = linear_act(x, w, b, relu)
-    return y[:, :N] if pn else y
+    from .linear import linear_act_padded
+    return linear_act_padded(x, w, b, relu)
 
 
 def _cols(w, k):

@@ -53,14 +53,20 @@ def _hipcc():
             return c
 
 
+INCLUDE = os.path.join(HERE, '..', 'include')
+
+
+def _headers():
+    """every header a source may include (csrc/*.h, include/*.h), from the directory listings: a new one needs no entry anywhere"""
+    return [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in sorted(os.listdir(d)) if f.endswith('.h')]
+
+
 def sources_hash():
-    """sha256 over the library's sources (csrc/*, the public header, this recipe) in a fixed order"""
+    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the public headers, this recipe) in a fixed order"""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')))
-    for f in files + [os.path.join(HERE, '..', 'include', 'xrnerf_mi355.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'),
-                      os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'),
-                      os.path.join(HERE, '..', 'include', 'xrnerf_mi355_aninerf.h'), os.path.abspath(__file__)]:
+    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
+    for f in files + _headers() + [os.path.abspath(__file__)]:
         h.update(os.path.basename(f).encode() + b'\0')
         with open(f, 'rb') as fh:
             h.update(fh.read())
@@ -85,15 +91,12 @@ def _stale(dst, srcs):
 
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, 'xr_common.h'), os.path.join(CSRC, 'xr_mip_math.h'), os.path.join(CSRC, 'xr_hashgrid.h'),
-               os.path.join(CSRC, 'xr_scatter.h'), os.path.join(CSRC, 'xr_adam.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355.h'),
-               os.path.join(HERE, '..', 'include', 'xrnerf_mi355_bungee.h'), os.path.join(HERE, '..', 'include', 'xrnerf_mi355_vanilla.h'),
-               os.path.join(HERE, '..', 'include', 'xrnerf_mi355_aninerf.h'), os.path.abspath(__file__)]
     have_src = all(os.path.exists(os.path.join(CSRC, s)) for s in SOURCES)
     if not have_src:
         if os.path.exists(OUT):
             return OUT
         raise RuntimeError('xrnerf_amd/csrc sources missing and no prebuilt library')
+    headers = _headers() + [os.path.abspath(__file__)]
     jobs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

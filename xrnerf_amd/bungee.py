@@ -18,7 +18,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import builder, ops
+from . import builder, mlp_graph as G, ops
 from .builder import EMBEDDERS, MLPS, NETWORKS, RENDERS
 from .mip import MipSamples, resample_along_rays, sample_along_rays
 from .networks import BaseNerfNetwork, get_dist_info, img2mse, mse2psnr, recover_shape, unfold_batching
@@ -276,13 +276,16 @@ class BungeeNerfMLP(nn.Module):
         return data
 
 
+def _block_layout(k):
+    """block k's place in the flat parameter list of _block_params: (offset, trunk layers); 2 n_trunk + 8 tensors per block"""
+    return (0, 4) if k == 0 else (16 + 12 * (k - 1), 2)
+
+
 class _BungeeMlpFn(torch.autograd.Function):
-    """BungeeNerfMLP.run_mlp as one autograd node on the strided linear kernels (the pattern of vanilla._NerfMlpFn):
-      * the first trunk layer reads the embedding's first Kx = ceil4(input_ch) columns in place, its weight padded with zero columns
-        (the padding multiplies finite embedding values by 0: exact);
+    """BungeeNerfMLP.run_mlp as one autograd node over the shared trunk / view-head graph (mlp_graph.py, which explains the buffer
+    layouts; the pattern of vanilla._NerfMlpFn).  Here:
       * each residual block's input [x_pts | h] is ONE buffer: x_pts copied once, h written into it by the previous trunk's last layer;
-      * feature and alpha heads are one product that lands in the view layer's input buffer [feature | alpha 0 0 0 | dirs | 0];
-      * each block's rgb head writes its column range of raw [M, H, 4] through the output row stride, alpha is copied to column 3;
+      * each block's view head writes its column range of raw [M, H, 4] through the output row stride;
       * the backward runs block by block from the last; blocks at or above `live` heads have an exactly-zero output gradient (the
         renderer's heads above the stage), so their products are skipped and their parameters get zero tensors (Adam still moves
         them through its moments, as in the reference)."""
@@ -291,105 +294,48 @@ class _BungeeMlpFn(torch.autograd.Function):
     def forward(ctx, x, ic, idr, n_res, live, *params):
         xr, _ = ops._rows(x.detach())
         ps = [p.detach() for p in params]
-        M = xr.shape[0]
-        W, W2 = ps[0].shape[0], ps[8].shape[0]
-        Kx = (ic + 3) // 4 * 4
+        M, W, Kx = xr.shape[0], ps[0].shape[0], G.ceil4(ic)
         if xr.shape[1] < Kx or xr.shape[1] < ic + idr:
             raise ops._lib.XrError('BungeeNerfMLP: the embedding has %d columns, expected %d' % (xr.shape[1], ic + idr))
         H = n_res + 1
-        o_dir = W + 4
-        KV = o_dir + (idr + 3) // 4 * 4
-        dev = xr.device
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         x_pts, x_dir = xr[:, :Kx], xr[:, ic:ic + idr]
-        raw = new(M, H, 4)
+        raw = torch.empty((M, H, 4), dtype=torch.float32, device=xr.device)
         blocks = []
-        nxt = None                               # the next residual block's [x_pts | h] buffer
         h = x_pts
         for k in range(H):
-            off = 0 if k == 0 else 16 + 12 * (k - 1)
-            n_trunk = 4 if k == 0 else 2
+            off, n_trunk = _block_layout(k)
             tw = ps[off:off + 2 * n_trunk]
-            vw, vb, fw, fb, aw, ab, rw, rb = ps[off + 2 * n_trunk:off + 2 * n_trunk + 8]
-            w0 = tw[0]
-            w0p = w0.new_zeros((W, Kx + (0 if k == 0 else W)))
-            w0p[:, :ic] = w0[:, :ic]
-            if k > 0:
-                w0p[:, Kx:] = w0[:, ic:]
-            ws = [w0p] + [tw[2 * i] for i in range(1, n_trunk)]
+            nxt = None                           # the next residual block's [x_pts | h] buffer
             if k < H - 1:
-                nxt = new(M, Kx + W)
+                nxt = torch.empty((M, Kx + W), dtype=torch.float32, device=xr.device)
                 nxt[:, :Kx].copy_(x_pts)
-            acts = []
-            for i in range(n_trunk):
-                out = nxt[:, Kx:] if (i == n_trunk - 1 and k < H - 1) else None
-                y = ops.linear_forward(h, ws[i], tw[2 * i + 1], True, out=out)
-                acts.append((h, y))
-                h = y
-            V = new(M, KV)
-            wb = torch.cat([fw, aw, fw.new_zeros((3, W))], 0)
-            bb = torch.cat([fb, ab, fb.new_zeros((3,))], 0)
-            ops.linear_forward(h, wb, bb, False, out=V[:, :o_dir])
-            V[:, o_dir:o_dir + idr].copy_(x_dir)
-            if KV > o_dir + idr:
-                V[:, o_dir + idr:].zero_()
-            wv2 = vw.new_zeros((W2, KV))
-            wv2[:, :W] = vw[:, :W]
-            wv2[:, o_dir:o_dir + idr] = vw[:, W:]
-            hv = ops.linear_forward(V, wv2, vb, True)
-            wr2 = torch.cat([rw, rw.new_zeros((1, W2))], 0)
-            br2 = torch.cat([rb, rb.new_zeros((1,))], 0)
-            ops.linear_forward(hv, wr2, br2, False, out=raw[:, k, :])
-            raw[:, k, 3].copy_(V[:, W])
-            blocks.append(dict(acts=acts, ws=ws, V=V, hv=hv, wb=wb, wv2=wv2, wr2=wr2))
-            if k < H - 1:
-                h = nxt
-        ctx.cfg = (ic, idr, n_res, min(max(int(live), 0), H), W, Kx, o_dir)
+            trunk, y = G.trunk_forward(h, list(zip(tw[0::2], tw[1::2])), ic, out=None if nxt is None else nxt[:, Kx:])
+            head = G.view_head_forward(y, x_dir, ps[off + 2 * n_trunk:off + 2 * n_trunk + 8], raw[:, k, :])
+            blocks.append((trunk, y, head))
+            h = nxt
+        ctx.cfg = (ic, n_res, min(max(int(live), 0), H), Kx)
         ctx.blocks = blocks
         ctx.shapes = [p.shape for p in ps]
         return raw
 
     @staticmethod
     def backward(ctx, d_raw):
-        ic, idr, n_res, live, W, Kx, o_dir = ctx.cfg
-        blocks = ctx.blocks
+        ic, n_res, live, Kx = ctx.cfg
         d_raw = d_raw.contiguous()
         grads = [None] * len(ctx.shapes)
-        dev = d_raw.device
         d_next = None                             # gradient of the next block's [x_pts | h] input
         for k in range(n_res, -1, -1):
-            off = 0 if k == 0 else 16 + 12 * (k - 1)
-            n_trunk = 4 if k == 0 else 2
+            off, n_trunk = _block_layout(k)
             n_p = 2 * n_trunk + 8
             if k >= live:
                 for j in range(off, off + n_p):
-                    grads[j] = torch.zeros(ctx.shapes[j], dtype=torch.float32, device=dev)
+                    grads[j] = torch.zeros(ctx.shapes[j], dtype=torch.float32, device=d_raw.device)
                 continue
-            b = blocks[k]
-            dr = d_raw[:, k, :]
-            dwr2, dbr2 = ops.linear_backward_weight_bias(dr, None, b['hv'])
-            dhv = ops.linear_backward_input(dr, None, b['wr2'])
-            dwv2, dbv = ops.linear_backward_weight_bias(dhv, b['hv'], b['V'])
-            dV = ops.linear_backward_input(dhv, b['hv'], b['wv2'])
-            dV[:, W].copy_(dr[:, 3])
-            dyb = dV[:, :o_dir]
-            acts = b['acts']
-            dwb, dbb = ops.linear_backward_weight_bias(dyb, None, acts[-1][1])
-            dh = ops.linear_backward_input(dyb, None, b['wb'])
+            trunk, y, head = ctx.blocks[k]
+            grads[off + 2 * n_trunk:off + n_p], dh = G.view_head_backward(d_raw[:, k, :], head, y)
             if d_next is not None:
-                dh = dh + d_next[:, Kx:]
-            tg = [None] * (2 * n_trunk)
-            for i in range(n_trunk - 1, -1, -1):
-                xin, y = acts[i]
-                tg[2 * i], tg[2 * i + 1] = ops.linear_backward_weight_bias(dh, y, xin)
-                if i > 0 or k > 0:
-                    dh = ops.linear_backward_input(dh, y, b['ws'][i])
-            d_next = dh if k > 0 else None
-            dw0 = tg[0]
-            tg[0] = dw0[:, :ic].contiguous() if k == 0 else torch.cat([dw0[:, :ic], dw0[:, Kx:]], 1)
-            grads[off:off + 2 * n_trunk] = tg
-            dvw = torch.cat([dwv2[:, :W], dwv2[:, o_dir:o_dir + idr]], 1)
-            grads[off + 2 * n_trunk:off + n_p] = [dvw, dbv, dwb[:W], dbb[:W], dwb[W:W + 1], dbb[W:W + 1], dwr2[:3], dbr2[:3]]
+                dh = dh + d_next[:, Kx:]          # the trunk's output feeds its own head and the next block
+            grads[off:off + 2 * n_trunk], d_next = G.trunk_backward(dh, trunk, ic, first=k == 0)
         ctx.blocks = None
         return (None, None, None, None, None) + tuple(grads)
 

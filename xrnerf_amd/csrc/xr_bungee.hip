@@ -17,45 +17,11 @@
 // expressions the same way, not to the precision fp64 would give.
 #include "xr_common.h"
 #include "xr_mip_math.h"
+#include "xr_wave.h"
 
 #define BG_TILE 64
 #define BG_BLOCK 256
 #define BG_MAX_DIR_CH 64                 /* 3 + 6 multires_dirs <= 64: multires_dirs <= 10 */
-
-// ------------------------------------------------------------------------------------------ wave helpers (wave64)
-static __device__ inline double bg_incl_prod(double v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double o = __shfl_up(v, off, 64);
-        if (lane >= off) v *= o;
-    }
-    return v;
-}
-// exclusive prefix of an inclusive scan: the value of the lane below (1 for lane 0)
-static __device__ inline double bg_excl_of_prod(double incl) {
-    const double o = __shfl_up(incl, 1, 64);
-    return (threadIdx.x & 63) ? o : 1.0;
-}
-static __device__ inline double bg_incl_sum(double v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-static __device__ inline double bg_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-static __device__ inline float bg_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------ BungeeGetBounds + BungeeGetZvals
 struct BungeeZArgs {
@@ -246,8 +212,8 @@ __global__ void __launch_bounds__(BG_BLOCK) k_bungee_render_fwd(BungeeRenderArgs
         BungeeSample s;
         double f = 1.0;
         if (live) { s = bg_load(a, r, i, vnorm); f = (double)s.f; }
-        const double incl = bg_incl_prod(f);
-        const double excl = bg_excl_of_prod(incl);                       // all lanes take part in the shuffle
+        const double incl = xr_wave_incl_prod(f);
+        const double excl = xr_wave_excl_of_prod(incl);                       // all lanes take part in the shuffle
         if (live) {
             const float T = (float)(carry * excl);                       // exclusive: the prefix before this lane
             const float alpha = 1.f - expf(s.dd);
@@ -259,9 +225,9 @@ __global__ void __launch_bounds__(BG_BLOCK) k_bungee_render_fwd(BungeeRenderArgs
         }
         carry *= __shfl(incl, 63, 64);
     }
-    const float acc = bg_sum(acc_w), depth = bg_sum(acc_z);
+    const float acc = xr_wave_sum(acc_w), depth = xr_wave_sum(acc_z);
     float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = bg_sum(acc_c[c]);
+    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(acc_c[c]);
     if (lane == 0) {
         const float q = depth / acc;
         disp_out[r] = 1.f / (q != q ? q : fmaxf(1e-10f, q));          // torch.max propagates NaN
@@ -290,15 +256,15 @@ __global__ void __launch_bounds__(BG_BLOCK) k_bungee_render_bwd(BungeeRenderArgs
         BungeeSample s;
         double f = 1.0, wg = 0.0;
         if (live) { s = bg_load(a, r, i, vnorm); f = (double)s.f; }
-        const double incl = bg_incl_prod(f);
-        const double excl = bg_excl_of_prod(incl);
+        const double incl = xr_wave_incl_prod(f);
+        const double excl = xr_wave_excl_of_prod(incl);
         if (live) {
             const float w = (1.f - expf(s.dd)) * (float)(carry * excl);
             float gc = 0.f;
             for (int c = 0; c < 3; ++c) gc += g[c] * (bg_rgb(a, s.a_rgb[c]) - white);
             wg = (double)w * (double)gc;
         }
-        total += bg_sum(wg);
+        total += xr_wave_sum(wg);
         carry *= __shfl(incl, 63, 64);
     }
     // pass 2: gradients
@@ -311,15 +277,15 @@ __global__ void __launch_bounds__(BG_BLOCK) k_bungee_render_bwd(BungeeRenderArgs
         double f = 1.0, wg = 0.0;
         float w = 0.f, gc = 0.f, T = 0.f;
         if (live) { s = bg_load(a, r, i, vnorm); f = (double)s.f; }
-        const double incl = bg_incl_prod(f);
-        const double excl = bg_excl_of_prod(incl);
+        const double incl = xr_wave_incl_prod(f);
+        const double excl = xr_wave_excl_of_prod(incl);
         if (live) {
             T = (float)(carry * excl);
             w = (1.f - expf(s.dd)) * T;
             for (int c = 0; c < 3; ++c) gc += g[c] * (bg_rgb(a, s.a_rgb[c]) - white);
             wg = (double)w * (double)gc;
         }
-        const double incl_wg = bg_incl_sum(wg);
+        const double incl_wg = xr_wave_incl_sum(wg);
         if (live) {
             const double suffix = total - (carry_wg + incl_wg);
             const float d_alpha = (float)((double)(T * gc) - suffix / f);

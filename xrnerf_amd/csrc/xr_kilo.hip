@@ -23,6 +23,7 @@
 // Bound: fp32 MFMA (157.3 TFLOP/s; 12.2 kflop per evaluated sample + 3 padded K slots per Fourier group) for
 // k_kilo_mlp, HBM for the rest.
 #include "xr_common.h"
+#include "xr_wave.h"
 #include "xr_adam.h"            // adam1: the students' fused update
 #include "xr_mip_math.h"      // xr_mip_zval: GetZvals' linspace (datasets/pipelines/create.py:502-516)
 
@@ -598,21 +599,6 @@ __global__ void __launch_bounds__(64 * KB_WAVES) k_kilo_mlp_bwd(KiloBwdArgs b) {
 }
 
 // ------------------------------------------------------------------------------------------ NerfRender.forward
-__device__ inline double wave_incl_prod(double v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double o = __shfl_up(v, off, 64);
-        if (lane >= off) v *= o;
-    }
-    return v;
-}
-__device__ inline float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // renders/nerf_render.py:45-98, raw_noise_std = 0; z are sample POSITIONS; the last interval is 1e10.
 // net_of (nullable): rows with net_of < 0 were never written and count as raw = 0 (exactly what they contribute: alpha = 0,
 // weight = 0, transmittance factor 1) -- the sparse frame path reads 4 bytes per empty sample instead of 16.
@@ -652,10 +638,8 @@ __global__ void __launch_bounds__(256) k_nerf_render(const float4* __restrict__ 
             if (live && weights_out != nullptr) weights_out[(uint64_t)r * n_s + i] = 0.f;
             continue;
         }
-        const double incl = wave_incl_prod(fac);
-        // exclusive product without dividing (a factor can be exactly 0): shift the inclusive scan by one lane
-        double excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0;
+        const double incl = xr_wave_incl_prod(fac);
+        const double excl = xr_wave_excl_of_prod(incl);      // (a factor can be exactly 0)
         if (live) {
             const float w = alpha * (float)(carry * excl);
             if (weights_out != nullptr) weights_out[(uint64_t)r * n_s + i] = w;
@@ -667,9 +651,9 @@ __global__ void __launch_bounds__(256) k_nerf_render(const float4* __restrict__ 
         }
         carry *= __shfl(incl, 63, 64);
     }
-    const float acc = wave_sum_f(a_w), depth = wave_sum_f(a_z);
+    const float acc = xr_wave_sum(a_w), depth = xr_wave_sum(a_z);
     float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = wave_sum_f(a_c[c]);
+    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(a_c[c]);
     if (lane == 0) {
         const float q = depth / acc;
         const float m = (q != q) ? q : fmaxf(1e-10f, q);                 // torch.max propagates the NaN of 0/0

@@ -13,31 +13,11 @@
 // All HBM-streaming: bytes per unit are in DESIGN.md section 8.
 #include "xr_common.h"
 #include "xr_mip_math.h"
+#include "xr_wave.h"
 
 #define MIP_TILE 64
 #define MIP_BLOCK 256
 #define MIP_MAX_NZ 2048u
-
-// ------------------------------------------------------------------------------------------ wave helpers
-__device__ inline double wave_incl_scan(double v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------ GetZvals
 __global__ void k_mip_zvals(const float* __restrict__ near, const float* __restrict__ far, uint32_t n_rays,
@@ -144,7 +124,7 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_fwd(MipRenderArgs a, f
         MipSample s;
         double dd = 0.0;
         if (live) { s = mip_load_sample(a, r, i, dnorm); dd = (double)s.dd; }
-        const double incl = wave_incl_scan(dd);
+        const double incl = xr_wave_incl_sum(dd);
         if (live) {
             const float before = (float)(carry + (incl - dd));          // exclusive cumsum, rounded like torch's output
             const float w = (1.f - expf(-s.dd)) * expf(-before);
@@ -155,9 +135,9 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_fwd(MipRenderArgs a, f
         }
         carry += __shfl(incl, 63, 64);
     }
-    const float acc = wave_sum(acc_w), depth = wave_sum(acc_z);
+    const float acc = xr_wave_sum(acc_w), depth = xr_wave_sum(acc_z);
     float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = wave_sum(acc_c[c]);
+    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(acc_c[c]);
     if (lane == 0) {
         const float* z = a.z_vals + (uint64_t)r * (a.n_s + 1);
         float q = depth / acc;                                          // mipnerf_render.py:17-23
@@ -189,7 +169,7 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_bwd(MipRenderArgs a, c
         MipSample s;
         double dd = 0.0, wg = 0.0;
         if (live) { s = mip_load_sample(a, r, i, dnorm); dd = (double)s.dd; }
-        const double incl = wave_incl_scan(dd);
+        const double incl = xr_wave_incl_sum(dd);
         if (live) {
             const float before = (float)(carry + (incl - dd));
             const float w = (1.f - expf(-s.dd)) * expf(-before);
@@ -197,7 +177,7 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_bwd(MipRenderArgs a, c
             for (int c = 0; c < 3; ++c) gc += g[c] * (s.rgb[c] - white);
             wg = (double)w * (double)gc;
         }
-        total += wave_sum(wg);
+        total += xr_wave_sum(wg);
         carry += __shfl(incl, 63, 64);
     }
     // pass 2: gradients
@@ -210,14 +190,14 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_bwd(MipRenderArgs a, c
         double dd = 0.0, wg = 0.0;
         float w = 0.f, gc = 0.f, before = 0.f;
         if (live) { s = mip_load_sample(a, r, i, dnorm); dd = (double)s.dd; }
-        const double incl = wave_incl_scan(dd);
+        const double incl = xr_wave_incl_sum(dd);
         if (live) {
             before = (float)(carry + (incl - dd));
             w = (1.f - expf(-s.dd)) * expf(-before);
             for (int c = 0; c < 3; ++c) gc += g[c] * (s.rgb[c] - white);
             wg = (double)w * (double)gc;
         }
-        const double incl_wg = wave_incl_scan(wg);
+        const double incl_wg = xr_wave_incl_sum(wg);
         if (live) {
             const double suffix = total - (carry_wg + incl_wg);
             const float t_next = expf(-before) * expf(-s.dd);           // T_{k+1}
@@ -260,7 +240,7 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_resample(const float* __restr
         wb[i] = v;
         part += (double)v;
     }
-    float weight_sum = (float)wave_sum(part);
+    float weight_sum = (float)xr_wave_sum(part);
     const float padding = fmaxf(0.f, 1e-5f - weight_sum);             // mip.py:12-16
     const float pad_each = padding / (float)n;
     weight_sum = weight_sum + padding;
@@ -270,7 +250,7 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_resample(const float* __restr
         const uint32_t i = base + lane;
         double p = 0.0;
         if (i < n) p = (double)((wb[i] + pad_each) / weight_sum);
-        const double incl = wave_incl_scan(p);
+        const double incl = xr_wave_incl_sum(p);
         if (i + 1 < n) cdf[i + 1] = fminf(1.f, (float)(carry + incl));
         carry += __shfl(incl, 63, 64);
     }

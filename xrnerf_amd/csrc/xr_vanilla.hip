@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off: every expression is fp32 in the reference's operation order.
 #include "xr_common.h"
 #include "xr_mip_math.h"
+#include "xr_wave.h"
 #include "../../include/xrnerf_mi355_vanilla.h"
 
 #define VN_BLOCK 256
@@ -24,36 +25,6 @@
 #define VN_MAX_FREQS 16                    /* multires, multires_dirs <= 16: at most 99 columns per part */
 #define VN_MAX_S 4096u                     /* renderer: at most 64 sweeps (one carry per lane in the backward) */
 #define VN_PDF_MAX 1024u                   /* sample_pdf: S and N each */
-
-// ------------------------------------------------------------------------------------------ wave helpers (wave64)
-static __device__ inline double vn_incl_prod(double v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double o = __shfl_up(v, off, 64);
-        if (lane >= off) v *= o;
-    }
-    return v;
-}
-static __device__ inline double vn_incl_sum(double v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-static __device__ inline double vn_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-static __device__ inline float vn_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------ BaseEmbedder.forward
 struct VnEncArgs {
@@ -147,9 +118,8 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_fwd(VnRenderArgs a, fl
         VnSample s;
         double f = 1.0;
         if (live) { s = vn_load(a, r, i, dnorm); f = (double)s.f; }
-        const double incl = vn_incl_prod(f);
-        double excl = __shfl_up(incl, 1, 64);                              // exclusive product without dividing (a factor can be 1e-10)
-        if (lane == 0) excl = 1.0;
+        const double incl = xr_wave_incl_prod(f);
+        const double excl = xr_wave_excl_of_prod(incl);                    // all lanes take part in the shuffle
         if (live) {
             const float w = s.alpha * (float)(carry * excl);
             weights_out[(uint64_t)r * a.n_s + i] = w;
@@ -161,9 +131,9 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_fwd(VnRenderArgs a, fl
         }
         carry *= __shfl(incl, 63, 64);
     }
-    const float acc = vn_sum(a_w), depth = vn_sum(a_z);
+    const float acc = xr_wave_sum(a_w), depth = xr_wave_sum(a_z);
     float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = vn_sum(a_c[c]);
+    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(a_c[c]);
     if (lane == 0) {
         const float q = depth / acc;
         const float m = (q != q) ? q : fmaxf(1e-10f, q);                   // torch.max propagates the NaN of 0/0
@@ -189,7 +159,7 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_bwd(VnRenderArgs a, co
         for (uint32_t b = 0; b + 1 < n_sweeps; ++b) {
             if (lane == b) my_carry = carry;
             const uint32_t i = b * 64 + lane;                                // a full sweep: every lane is live
-            const double incl = vn_incl_prod((double)vn_load(a, r, i, dnorm).f);
+            const double incl = xr_wave_incl_prod((double)vn_load(a, r, i, dnorm).f);
             carry *= __shfl(incl, 63, 64);
         }
         if (lane == n_sweeps - 1) my_carry = carry;
@@ -209,9 +179,8 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_bwd(VnRenderArgs a, co
             G = ((g[0] * sg[0] + g[1] * sg[1]) + g[2] * sg[2]) - gw;
             ag = (double)s.alpha * (double)G;
         }
-        const double incl = vn_incl_prod(f);
-        double excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0;
+        const double incl = xr_wave_incl_prod(f);
+        const double excl = xr_wave_excl_of_prod(incl);
         const double T = __shfl(my_carry, (int)b, 64) * excl;
         // reverse inclusive scan of the maps x -> ag + f x: (F, A) of lane k covers samples k .. min(k + 2 off - 1, 63)
         double F = f, A = ag;
@@ -257,13 +226,13 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_sample_pdf(const float* __res
     for (uint32_t i = lane; i < P; i += 64) buf[i] = i < S ? z[i] : __uint_as_float(0x7f800000u);       // +inf behind the data
     double part = 0.0;
     for (uint32_t i = lane; i < n; i += 64) part += (double)(w[i] + 1e-5f);
-    const float wsum = (float)vn_sum(part);
+    const float wsum = (float)xr_wave_sum(part);
     double carry = 0.0;
     for (uint32_t base = 0; base < n; base += 64) {
         const uint32_t i = base + lane;
         double p = 0.0;
         if (i < n) p = (double)((w[i] + 1e-5f) / wsum);
-        const double incl = vn_incl_sum(p);
+        const double incl = xr_wave_incl_sum(p);
         if (i < n) cdf[i + 1] = (float)(carry + incl);
         carry += __shfl(incl, 63, 64);
     }

@@ -45,8 +45,8 @@ def linear_act_padded(x, weight, bias=None, relu=False):
     """linear_act for any K / N on the device: zero columns / rows bring both to multiples of 4 (exact: the padded
     products are 0 * 0, the padded outputs are dropped), so narrow heads (1, 3 outputs) and the 283-wide view layer stay
     on the MFMA kernel instead of hipBLASLt's K = 1 / K = 3 gradient GEMMs (0.4-0.7 ms each at 131072 rows)"""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0):
-        return linear_act(x, weight, bias, relu)
+    if not (ops._on_device(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0):
+        return linear_act(x, weight, bias, relu)             # (torch's own linear: linear_ok refuses the same tensors)
     N, K = weight.shape
     pk, pn = (-K) % 4, (-N) % 4
     if pk:

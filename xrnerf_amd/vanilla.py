@@ -179,105 +179,54 @@ class NerfMLP(nn.Module):
 
 
 class _NerfMlpFn(torch.autograd.Function):
-    """NerfMLP.run_mlp on the device (nerf_mlp.py:62-94) as one autograd node.  Same products, same order of the concatenated inputs; what is
-    gone is the glue around them (19 % of the Mip-NeRF step's GPU time in round 5: cat / split / pad copies, masked copies, two reductions per
-    layer, per-layer autograd nodes):
-      * the skip connection's [x_pts | h] is a buffer the skip layer writes its output INTO (xr_linear_forward with an output row stride);
-        the gradient of that output is the same column range of the next layer's input gradient (row stride on dy and the relu mask);
-      * feature and alpha heads are one product whose output lands in the view layer's input buffer [feature | alpha 0 0 0 | dir | 0]; the
-        view layer's weight has zero columns under alpha and the padding (exact: the products are w * 0), so nothing is concatenated;
-      * the rgb head has a fourth, zero output row; the node's output [rgb | alpha] is that product with alpha copied into column 3;
-      * every layer's weight and bias gradient come from one launch and one reduction over the M ranges (ops.linear_backward_weight_bias).
+    """NerfMLP.run_mlp on the device (nerf_mlp.py:62-94) as one autograd node over the shared trunk / view-head graph (mlp_graph.py, which
+    explains the buffer layouts).  Here: the trunk cut into runs that end at a skip layer, each writing into the [x_pts | h] buffer the
+    next run reads, and the parameter layout (D trunk layers, then views, feature, alpha, rgb).
     x: the embedded batch [M, input_ch + input_ch_dirs], rows 16-byte aligned (ops.mip_encode pads its rows for this; otherwise one copy)."""
 
     @staticmethod
     def forward(ctx, x, skips, ic, idr, *params):
-        from . import ops
+        from . import mlp_graph as G, ops
         D = (len(params) - 8) // 2
-        vw, vb, fw, fb, aw, ab, rw, rb = [p.detach() for p in params[2 * D:]]
-        pts = [p.detach() for p in params[:2 * D]]
+        ps = [p.detach() for p in params]
         xr, _ = ops._rows(x.detach())
-        M, W, W2 = xr.shape[0], pts[0].shape[0], vw.shape[0]
-        # input_ch not a multiple of 4 (63 in config #1): the trunk reads Kx = ceil4(input_ch) columns of x in place and the weights get
-        # zero columns there (the columns hold finite values -- the first direction features or the encoder's zero padding: w * x = 0 exactly)
-        Kx = (ic + 3) // 4 * 4
+        M, W, Kx = xr.shape[0], ps[0].shape[0], G.ceil4(ic)
         if xr.shape[1] < Kx or xr.shape[1] < ic + idr:
             raise ops._lib.XrError('NerfMLP: the embedding has %d columns, expected %d' % (xr.shape[1], ic + idr))
         x_pts, x_dir = xr[:, :Kx], xr[:, ic:ic + idr]
-        wts = [pts[2 * i] for i in range(D)]
-        if Kx != ic:
-            for i in range(D):
-                if i == 0 or (i - 1) in skips:
-                    wp = wts[i].new_zeros((W, wts[i].shape[1] + Kx - ic))
-                    wp[:, :ic] = wts[i][:, :ic]
-                    wp[:, Kx:] = wts[i][:, ic:]
-                    wts[i] = wp
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=xr.device)
-        acts, h = [], x_pts
-        for i in range(D):
-            if i in skips:
-                cat = new(M, Kx + W)
+        # the trunk in runs [lo, hi) that end behind a skip layer; a run's first layer reads x_pts (zero weight columns under its padding)
+        ends = sorted({i + 1 for i in skips if 0 <= i < D - 1} | {D})
+        runs = list(zip([0] + ends[:-1], ends))
+        trunks, h = [], x_pts
+        for lo, hi in runs:
+            cat = None                           # the next run's [x_pts | h] buffer
+            if hi < D:
+                cat = torch.empty((M, Kx + W), dtype=torch.float32, device=xr.device)
                 cat[:, :Kx].copy_(x_pts)
-                y = ops.linear_forward(h, wts[i], pts[2 * i + 1], True, out=cat[:, Kx:])
-                acts.append((h, y))
-                h = cat
-            else:
-                y = ops.linear_forward(h, wts[i], pts[2 * i + 1], True)
-                acts.append((h, y))
-                h = y
-        o_dir = W + 4
-        KV = o_dir + (idr + 3) // 4 * 4
-        V = new(M, KV)
-        wb = torch.cat([fw, aw, fw.new_zeros((3, W))], 0)
-        bb = torch.cat([fb, ab, fb.new_zeros((3,))], 0)
-        ops.linear_forward(h, wb, bb, False, out=V[:, :o_dir])
-        V[:, o_dir:o_dir + idr].copy_(x_dir)
-        if KV > o_dir + idr:
-            V[:, o_dir + idr:].zero_()
-        wv2 = vw.new_zeros((W2, KV))
-        wv2[:, :W] = vw[:, :W]
-        wv2[:, o_dir:o_dir + idr] = vw[:, W:]
-        hv = ops.linear_forward(V, wv2, vb, True)
-        wr2 = torch.cat([rw, rw.new_zeros((1, W2))], 0)
-        br2 = torch.cat([rb, rb.new_zeros((1,))], 0)
-        raw = ops.linear_forward(hv, wr2, br2, False)
-        raw[:, 3].copy_(V[:, W])
-        ctx.cfg = (tuple(skips), ic, idr, D, W, W2, o_dir, KV, Kx)
-        ctx.acts, ctx.h_last, ctx.V, ctx.hv = acts, h, V, hv
-        ctx.w = (wts, wb, wv2, wr2)
+            state, y = G.trunk_forward(h, list(zip(ps[2 * lo:2 * hi:2], ps[2 * lo + 1:2 * hi:2])), ic, out=None if cat is None else cat[:, Kx:])
+            trunks.append(state)
+            h = y if cat is None else cat
+        raw = torch.empty((M, 4), dtype=torch.float32, device=xr.device)
+        ctx.head = G.view_head_forward(h, x_dir, ps[2 * D:], raw)
+        ctx.cfg = (ic, Kx, runs)
+        ctx.trunks, ctx.h_last = trunks, h
         return raw
 
     @staticmethod
     def backward(ctx, d_raw):
-        from . import ops
+        from . import mlp_graph as G, ops
         if ctx.needs_input_grad[0]:
             raise ops._lib.XrError('_NerfMlpFn has no gradient with respect to its input: NerfMLP.run_mlp takes the per-layer graph for '
                                    'an input that requires one')
-        skips, ic, idr, D, W, W2, o_dir, KV, Kx = ctx.cfg
-        wts, wb, wv2, wr2 = ctx.w
-        acts, V, hv = ctx.acts, ctx.V, ctx.hv
-        d_raw = d_raw.contiguous()
-        dwr2, dbr2 = ops.linear_backward_weight_bias(d_raw, None, hv)
-        dhv = ops.linear_backward_input(d_raw, None, wr2)
-        dwv2, dbv = ops.linear_backward_weight_bias(dhv, hv, V)
-        dV = ops.linear_backward_input(dhv, hv, wv2)
-        dV[:, W].copy_(d_raw[:, 3])                          # alpha's gradient joins the feature gradient: one product for both heads
-        dyb = dV[:, :o_dir]
-        dwb, dbb = ops.linear_backward_weight_bias(dyb, None, ctx.h_last)
-        dh = ops.linear_backward_input(dyb, None, wb)
-        grads = [None] * (2 * D)
-        for i in range(D - 1, -1, -1):
-            xin, y = acts[i]
-            dy = dh[:, Kx:] if i in skips else dh
-            dw, grads[2 * i + 1] = ops.linear_backward_weight_bias(dy, y, xin)
-            if Kx != ic and (i == 0 or (i - 1) in skips):
-                dw = torch.cat([dw[:, :ic], dw[:, Kx:]], 1)            # without the zero columns of the padded weight
-            grads[2 * i] = dw
-            if i > 0:
-                dh = ops.linear_backward_input(dy, y, wts[i])
-        dvw = torch.cat([dwv2[:, :W], dwv2[:, o_dir:o_dir + idr]], 1)
-        ctx.acts = ctx.h_last = ctx.V = ctx.hv = None
-        return (None, None, None, None) + tuple(grads) + (dvw, dbv, dwb[:W], dbb[:W], dwb[W:W + 1], dbb[W:W + 1], dwr2[:3], dbr2[:3])
+        ic, Kx, runs = ctx.cfg
+        head_grads, dh = G.view_head_backward(d_raw.contiguous(), ctx.head, ctx.h_last)
+        grads = [None] * (2 * runs[-1][1])
+        for (lo, hi), state in zip(reversed(runs), reversed(ctx.trunks)):
+            grads[2 * lo:2 * hi], dh_in = G.trunk_backward(dh, state, ic, first=lo == 0)
+            if lo > 0:
+                dh = dh_in[:, Kx:]                             # the skip layer's output is that column range of [x_pts | h]
+        ctx.trunks = ctx.h_last = ctx.head = None
+        return (None, None, None, None) + tuple(grads) + tuple(head_grads)
 
 
 # ------------------------------------------------------------------ classic volume rendering
