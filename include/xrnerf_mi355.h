@@ -675,6 +675,9 @@ int xr_linear_forward(const float* x, uint32_t ldx, const float* w, const float*
  * lddy: row stride of dy and of mask_src */
 int xr_linear_backward_input(const float* dy, uint32_t lddy, const float* mask_src, const float* w, int w_transposed, uint32_t M, uint32_t N,
                              uint32_t K, float* dx, void* stream);
+/* The arithmetic of the calling thread's following xr_linear_* launches: 0 = the XR_GEMM_F32 environment variable decides (the default),
+ * 1 = split2, 2 = bf16x3, 3 = bf16x3all, 4 = mfma (the exact-fp32 MFMA kernel throughout).  Returns the previous mode, or XR_EINVAL. */
+int xr_linear_arithmetic(int mode);
 /* M ranges of the weight gradient of an N x K layer; N == K == 0: of the bias gradient alone (xr_linear_backward_bias) */
 uint32_t xr_linear_backward_splits(uint32_t M, uint32_t N, uint32_t K);
 /* db_partials (nullable): weight and bias gradient in one launch: db_partials [splits,N] over the SAME M ranges as dw_partials (taken from

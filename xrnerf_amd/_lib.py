@@ -149,6 +149,7 @@ SIGNATURES = {
     'xr_linear_forward': (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _vp, _u32, _vp]),
     'xr_linear_backward_input': (_i32, [_vp, _u32, _vp, _vp, _i32, _u32, _u32, _u32, _vp, _vp]),
     'xr_linear_backward_splits': (_u32, [_u32, _u32, _u32]),
+    'xr_linear_arithmetic': (_i32, [_i32]),
     'xr_linear_backward_bias': (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
     'xr_sum_partials': (_i32, [_vp, _u32, _sz, _u32, _vp, _vp]),
     'xr_linear_backward_weight': (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp]),
@@ -191,6 +192,21 @@ ANINERF_SIGNATURES = {
     'xr_ani_skin_forward': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     'xr_ani_skin_backward': (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     'xr_ani_encode_backward': (_i32, [_vp, _vp, _u32, _u32, _i32, _vp, _vp]),
+}
+
+# NeuralBody (csrc/xr_neuralbody.hip, declared in include/xrnerf_mi355_neuralbody.h): a table of its own as well
+NEURALBODY_SIGNATURES = {
+    'xr_nb_layout': (_i32, [_u32, _i32, _i32, _i32, _vp]),
+    'xr_nb_build_rows_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'xr_nb_build_rows': (_i32, [_vp, _u32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'xr_nb_subm_table': (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _vp, _vp]),
+    'xr_nb_down_tables': (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'xr_nb_conv': (_i32, [_vp, _vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'xr_nb_conv_weight_grad_workspace_bytes': (_sz, [_u32, _i32, _i32]),
+    'xr_nb_conv_weight_grad': (_i32, [_vp, _vp, _vp, _u32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    'xr_nb_sample_forward': (_i32, [_vp, _vp, _vp, _vp, _f, _i32, _i32, _i32, _vp, _vp, _u32, _vp, _u32, _vp]),
+    'xr_nb_sample_backward_workspace_bytes': (_sz, [_vp]),
+    'xr_nb_sample_backward': (_i32, [_vp, _vp, _vp, _vp, _f, _i32, _i32, _i32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
@@ -249,7 +265,7 @@ def load():
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
-            list(ANINERF_SIGNATURES.items()):
+            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -39,6 +39,9 @@ SOURCES = {
     # Animatable-NeRF stages (closest vertex, selection, blend head, skinning, encode backward): the nearest-vertex decision is made on
     # d2 = (dx dx + dy dy) + dz dz, which must round like its fp32 tensor-op restatement
     'xr_aninerf.hip': ['-ffp-contract=off'],
+    # NeuralBody stages (sparse structure, 3x3x3 sparse convolution, feature sampling): the sampling coordinates ((c + 1) / 2) (size - 1)
+    # and the trilinear weights must round like torch's grid_sample, whose corner decision is a floorf of them
+    'xr_neuralbody.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

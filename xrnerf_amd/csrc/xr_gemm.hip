@@ -534,6 +534,21 @@ __global__ void __launch_bounds__(256, 2) k_gemm_split_kt(GemmArgs g) {
     }
 }
 
+// xr_linear_arithmetic: the calling thread's choice of arithmetic for the launches below, in front of XR_GEMM_F32 (0 = the environment
+// decides).  A module whose parity bars are fp32's own (NB_NeRFMLP) takes the fp32-MFMA kernel this way, without
+// touching the process environment that every other caller reads.
+static thread_local int g_gemm_arith = 0;
+static inline const char* gemm_arith_env() {
+    static const char* const names[5] = {nullptr, "split2", "bf16x3", "bf16x3all", "mfma"};
+    return g_gemm_arith > 0 ? names[g_gemm_arith] : getenv("XR_GEMM_F32");
+}
+extern "C" int xr_linear_arithmetic(int mode) {
+    XR_REQUIRE(mode >= 0 && mode <= 4, "mode must be 0 (XR_GEMM_F32 decides), 1 split2, 2 bf16x3, 3 bf16x3all or 4 mfma");
+    const int prev = g_gemm_arith;
+    g_gemm_arith = mode;
+    return prev;
+}
+
 static int gemm_launch(GemmArgs g, uint32_t splits, void* stream) {
     XR_REQUIRE(g.A && g.B && g.C, "null pointer");
     XR_REQUIRE(g.lda % 4 == 0 && g.ldb % 4 == 0, "leading dimensions must be multiples of 4 floats (16-byte vector loads)");
@@ -554,7 +569,7 @@ static int gemm_launch(GemmArgs g, uint32_t splits, void* stream) {
     // Anything else is an error.  NOTE the split kernels' operand range: an Inf (or a magnitude within 2^-8 of FLT_MAX, whose
     // bf16 head rounds to Inf; beyond 65504 for fp16 parts) turns into NaN inside the split (Inf - Inf); the fp32-MFMA kernel propagates it
     // like an fmaf chain.
-    const char* env = getenv("XR_GEMM_F32");
+    const char* env = gemm_arith_env();
     const bool dflt = !env || !env[0] || strcmp(env, "split2") == 0;
     const bool b3 = env && strcmp(env, "bf16x3") == 0;
     const bool all = env && strcmp(env, "bf16x3all") == 0;
@@ -688,7 +703,7 @@ extern "C" int xr_linear_backward_weight(const float* dy, uint32_t lddy, const f
     if (ldx == 0) ldx = K;
     if (part_stride == 0) part_stride = (size_t)N * K;
     XR_REQUIRE(lddy >= N && ldx >= K && part_stride >= (size_t)N * K && part_stride % 4 == 0, "bad stride");
-    const char* env = getenv("XR_GEMM_F32");
+    const char* env = gemm_arith_env();
     if (db_partials && env && strcmp(env, "bf16x3all") == 0) {   // that measurement mode has no column sums in its kernel: two launches
         GemmArgs g0{dy, x, dw_partials, nullptr, mask_src, N, K, M, lddy, ldx, K, 1, 1, 0, 0, part_stride, 0, nullptr};
         const int rc = gemm_launch(g0, splits, stream);

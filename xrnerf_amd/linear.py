@@ -34,19 +34,34 @@ class _LinearAct(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def linear_act(x, weight, bias=None, relu=False):
+class _LinearActExact(torch.autograd.Function):
+    """_LinearAct with all three products on the exact-fp32 MFMA kernel (ops.linear_arithmetic('mfma')), forward and backward: for
+    modules whose parity bars are fp32's own summation-order error, below the default split arithmetic's 2^-16 per gradient product"""
+
+    @staticmethod
+    def forward(ctx, x, w, b, relu):
+        with ops.linear_arithmetic('mfma'):
+            return _LinearAct.forward(ctx, x, w, b, relu)
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.linear_arithmetic('mfma'):
+            return _LinearAct.backward(ctx, dy)
+
+
+def linear_act(x, weight, bias=None, relu=False, exact=False):
     if ops.linear_ok(x, weight):
-        return _LinearAct.apply(x, weight, bias, relu)
+        return (_LinearActExact if exact else _LinearAct).apply(x, weight, bias, relu)
     y = F.linear(x, weight, bias)
     return F.relu(y) if relu else y
 
 
-def linear_act_padded(x, weight, bias=None, relu=False):
+def linear_act_padded(x, weight, bias=None, relu=False, exact=False):
     """linear_act for any K / N on the device: zero columns / rows bring both to multiples of 4 (exact: the padded
     products are 0 * 0, the padded outputs are dropped), so narrow heads (1, 3 outputs) and the 283-wide view layer stay
     on the MFMA kernel instead of hipBLASLt's K = 1 / K = 3 gradient GEMMs (0.4-0.7 ms each at 131072 rows)"""
     if not (ops._on_device(x) and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0):
-        return linear_act(x, weight, bias, relu)             # (torch's own linear: linear_ok refuses the same tensors)
+        return linear_act(x, weight, bias, relu, exact)      # (torch's own linear: linear_ok refuses the same tensors)
     N, K = weight.shape
     pk, pn = (-K) % 4, (-N) % 4
     if pk:
@@ -55,5 +70,5 @@ def linear_act_padded(x, weight, bias=None, relu=False):
     if pn:
         weight = F.pad(weight, (0, 0, 0, pn))
         bias = F.pad(bias, (0, pn)) if bias is not None else None
-    y = linear_act(x, weight, bias, relu)
+    y = linear_act(x, weight, bias, relu, exact)
     return y[:, :N] if pn else y

@@ -1358,6 +1358,27 @@ def linear_ok(x, w):
             and x.shape[1] % 4 == 0 and w.shape[0] % 4 == 0 and x.shape[0] > 0)
 
 
+LINEAR_ARITHMETIC = {None: 0, 'split2': 1, 'bf16x3': 2, 'bf16x3all': 3, 'mfma': 4}      # xr_linear_arithmetic
+
+
+class linear_arithmetic:
+    """context manager: this thread's linear-kernel launches inside it use the given arithmetic whatever XR_GEMM_F32 says
+    ('mfma' = the exact-fp32 MFMA kernel for all three products); the previous choice comes back on exit"""
+
+    def __init__(self, kind):
+        self.mode = LINEAR_ARITHMETIC[kind]
+
+    def __enter__(self):
+        self.prev = _lib.load().xr_linear_arithmetic(self.mode)
+        if self.prev < 0:
+            _lib.check(self.prev, 'xr_linear_arithmetic')
+        return self
+
+    def __exit__(self, *exc):
+        _lib.load().xr_linear_arithmetic(self.prev)
+        return False
+
+
 def _rows(t):
     """(tensor as the linear kernels take it, row stride): a [M, C] fp32 matrix whose rows are contiguous and start on 16-byte boundaries --
     dense, or a column range of a wider buffer.  Anything else is copied."""
@@ -1814,3 +1835,185 @@ def ani_encode_backward(pts, grad, multires):
         _lib.check(_lib.load().xr_ani_encode_backward(_ptr(pts), C.c_void_p(grad.data_ptr()), grad.stride(0) if N else cp, N, int(multires),
                                                       _ptr(out), _stream()), 'xr_ani_encode_backward')
     return out
+
+
+# ---------------------------------------------------------------- NeuralBody (configs/neuralbody/nb_zjumocap_*.py)
+NB_LEVELS = 5                   # XR_NB_LEVELS
+NB_TAPS = 27                    # XR_NB_TAPS
+NB_MAX_CELLS = 1 << 26          # XR_NB_MAX_CELLS
+NB_FEATURES = 352               # XR_NB_FEATURES
+NB_LEVEL_CHANNELS = (32, 64, 128, 128)
+
+
+def neuralbody_kernels_available():
+    """the loaded library handle has xr_neuralbody.hip's entry points (a handle made of the host builds of other sources may not:
+    the modules of neuralbody.py then keep their tensor-op path)"""
+    return hasattr(_lib.load(), 'xr_nb_conv')
+
+
+def _nb_dims(out_sh):
+    D, H, W = (int(v) for v in out_sh)
+    return D, H, W
+
+
+def nb_layout(V, out_sh):
+    """-> (volume offsets [5], row-list offsets [5], total volume ints, total list ints) of xr_nb_build_rows' two buffers"""
+    D, H, W = _nb_dims(out_sh)
+    out = (C.c_uint64 * 12)()
+    _lib.check(_lib.load().xr_nb_layout(int(V), D, H, W, C.cast(out, C.c_void_p)), 'xr_nb_layout')
+    return [int(v) for v in out[0:5]], [int(v) for v in out[5:10]], int(out[10]), int(out[11])
+
+
+def nb_build_rows(coord, out_sh):
+    """the five levels of a frame from the voxel coordinates coord [V,3] int32 (z, y, x) in the volume out_sh = (D, H, W):
+    -> (vols: five int32 index volumes [cells_l] (row of each cell, -1 where empty), rows: five int32 lists of active cells in
+    ascending linear index, vert_row [V] int32, counts: five ints).  ONE read of the counts from the device."""
+    coord = _i32c(coord).reshape(-1, 3)
+    V = coord.shape[0]
+    D, H, W = _nb_dims(out_sh)
+    lib = _lib.load()
+    vo, ro, nv, nr = nb_layout(V, out_sh)
+    dev = coord.device
+    vol = torch.empty((nv,), dtype=torch.int32, device=dev)
+    rows = torch.empty((max(nr, 1),), dtype=torch.int32, device=dev)
+    vert_row = torch.empty((V,), dtype=torch.int32, device=dev)
+    counts = torch.zeros((NB_LEVELS,), dtype=torch.int32, device=dev)
+    ws = _ws(dev, int(lib.xr_nb_build_rows_workspace_bytes(D, H, W)), 'nb_rows')
+    _ptr(coord)
+    with _span('xr_nb_build_rows', V):
+        _lib.check(lib.xr_nb_build_rows(_ptr(coord), V, D, H, W, _ptr(vol), _ptr(rows), _ptr(vert_row), _ptr(counts),
+                                        C.c_void_p(ws.data_ptr()), ws.numel(), _stream()), 'xr_nb_build_rows')
+    n = [int(v) for v in counts.tolist()]
+    ends = vo[1:] + [nv]
+    return [vol[vo[l]:ends[l]] for l in range(NB_LEVELS)], [rows[ro[l]:ro[l] + n[l]] for l in range(NB_LEVELS)], vert_row, n
+
+
+def nb_subm_table(vol, rows, dims):
+    """[n,27] int32: the row of cell p + k - 1 for every row p of a level with dims (D, H, W), -1 where empty or outside"""
+    D, H, W = _nb_dims(dims)
+    n = rows.shape[0]
+    nbr = torch.empty((n, NB_TAPS), dtype=torch.int32, device=rows.device)
+    _ptr(vol)
+    with _span('xr_nb_subm_table', n):
+        _lib.check(_lib.load().xr_nb_subm_table(_ptr(vol), _ptr(_i32c(rows)), n, D, H, W, _ptr(nbr), _stream()), 'xr_nb_subm_table')
+    return nbr
+
+
+def nb_down_tables(vol_in, rows_in, vol_out, rows_out, dims_in):
+    """the strided step's tables: (out_tab [n_out,27] input row at 2 o - 1 + k, in_tab [n_in,27] output row whose tap k reads input i)"""
+    D, H, W = _nb_dims(dims_in)
+    n_in, n_out = rows_in.shape[0], rows_out.shape[0]
+    dev = rows_in.device
+    out_tab = torch.empty((n_out, NB_TAPS), dtype=torch.int32, device=dev)
+    in_tab = torch.empty((n_in, NB_TAPS), dtype=torch.int32, device=dev)
+    _ptr(vol_in)
+    with _span('xr_nb_down_tables', n_in):
+        _lib.check(_lib.load().xr_nb_down_tables(_ptr(vol_in), _ptr(_i32c(rows_in)), n_in, _ptr(vol_out), _ptr(_i32c(rows_out)), n_out,
+                                                 D, H, W, _ptr(out_tab), _ptr(in_tab), _stream()), 'xr_nb_down_tables')
+    return out_tab, in_tab
+
+
+def _nb_weight(w):
+    w = _f32c(w)
+    if w.dim() == 5 and tuple(w.shape[1:4]) == (3, 3, 3):
+        w = w.reshape(w.shape[0], NB_TAPS, w.shape[4])
+    if w.dim() != 3 or w.shape[1] != NB_TAPS:
+        raise _lib.XrError('a sparse-convolution weight is [Cout, 3, 3, 3, Cin]')
+    return w
+
+
+def nb_conv(x, tab, w, transposed=False, flip=False):
+    """out [n, c_out] = sum_k x[tab[:, k']] Wk with rows of tab = -1 reading as 0; w [Cout, 3, 3, 3, Cin].  transposed: the input
+    gradient (x = dL/dout [*, Cout], out [n, Cin]); flip: k' = 26 - k (the submanifold input gradient on the forward table)"""
+    x, w, tab = _f32c(x), _nb_weight(w), _i32c(tab)
+    n = tab.shape[0]
+    cin, cout = (w.shape[0], w.shape[2]) if transposed else (w.shape[2], w.shape[0])
+    if x.dim() != 2 or x.shape[1] != cin or tab.dim() != 2 or tab.shape[1] != NB_TAPS:
+        raise _lib.XrError('nb_conv: x must be [*, %d] and tab [n, 27]' % cin)
+    out = torch.empty((n, cout), dtype=torch.float32, device=x.device)
+    _ptr(w)
+    with _span('xr_nb_conv', n):
+        _lib.check(_lib.load().xr_nb_conv(_ptr(x), _ptr(tab), _ptr(w), n, cin, cout, int(bool(transposed)), int(bool(flip)), _ptr(out),
+                                          _stream()), 'xr_nb_conv')
+    return out
+
+
+def nb_conv_weight_grad(x, tab, g):
+    """dW [Cout, 3, 3, 3, Cin] = sum_r g[r]^T x[tab[r, k]] per tap (tab: the forward table of the n rows of g)"""
+    x, g, tab = _f32c(x), _f32c(g), _i32c(tab)
+    n, cin, cout = tab.shape[0], x.shape[1], g.shape[1]
+    if g.shape[0] != n or tab.shape[1] != NB_TAPS:
+        raise _lib.XrError('nb_conv_weight_grad: g must be [n, Cout] for tab [n, 27]')
+    dw = torch.zeros((cout, 3, 3, 3, cin), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    ws = _ws(x.device, int(lib.xr_nb_conv_weight_grad_workspace_bytes(n, cin, cout)), 'nb_wgrad')
+    _ptr(g)
+    with _span('xr_nb_conv_weight_grad', n):
+        _lib.check(lib.xr_nb_conv_weight_grad(_ptr(x), _ptr(tab), _ptr(g), n, cin, cout, _ptr(dw), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                              _stream()), 'xr_nb_conv_weight_grad')
+    return dw
+
+
+def _nb_ptr4(ts):
+    arr = (C.c_void_p * 4)()
+    for l, t in enumerate(ts):
+        arr[l] = t.data_ptr() if (t is not None and t.numel()) else None
+    return arr
+
+
+def _nb_sample_common(pts, R, T, min_xyz, vols, feats_or_counts):
+    pts = _f32c(pts).reshape(-1, 3)
+    R, T, min_xyz = _f32c(R).reshape(9), _f32c(T).reshape(3), _f32c(min_xyz).reshape(3)
+    if len(vols) != 4 or len(feats_or_counts) != 4:
+        raise _lib.XrError('sampling takes the four levels after conv1..conv4')
+    for t in (pts, R, T, min_xyz) + tuple(vols):
+        _ptr(t)
+    return pts, R, T, min_xyz, [_i32c(v) for v in vols]
+
+
+def nb_sample_forward(pts, R, T, min_xyz, voxel, out_sh, vols, feats, out=None):
+    """grid_sample (zeros padding, align_corners) of the four levels' sparse rows at the world points pts [N,3], through the levels'
+    index volumes: -> [N, 352], or written into the first 352 columns of `out` [N, >= 352] (a row stride that is a multiple of 4)"""
+    pts, R, T, min_xyz, vols = _nb_sample_common(pts, R, T, min_xyz, vols, feats)
+    feats = [_f32c(f) for f in feats]
+    for f, c in zip(feats, NB_LEVEL_CHANNELS):
+        if f.dim() != 2 or f.shape[1] != c:
+            raise _lib.XrError('the sampled levels have 32, 64, 128 and 128 channels')
+    N = pts.shape[0]
+    D, H, W = _nb_dims(out_sh)
+    if out is None:
+        out = torch.empty((N, NB_FEATURES), dtype=torch.float32, device=pts.device)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != N or out.shape[1] < NB_FEATURES or (N and out.stride(1) != 1):
+        raise _lib.XrError('nb_sample_forward: out must be float32 [N, >= 352] with unit column stride')
+    if not _on_device(out):
+        _ptr(out)
+    with _span('xr_nb_sample_forward', N):
+        _lib.check(_lib.load().xr_nb_sample_forward(_ptr(pts), _ptr(R), _ptr(T), _ptr(min_xyz), float(voxel), D, H, W,
+                                                    C.cast(_nb_ptr4(vols), C.c_void_p), C.cast(_nb_ptr4(feats), C.c_void_p), N,
+                                                    C.c_void_p(out.data_ptr()), out.stride(0) if N else NB_FEATURES, _stream()),
+                   'xr_nb_sample_forward')
+    return out
+
+
+def nb_sample_backward(pts, R, T, min_xyz, voxel, out_sh, vols, n_rows, grad):
+    """the gradient of the four levels' rows from grad [N, >= 352] (read in place at its row stride): four tensors [n_rows[l], C_l]"""
+    pts, R, T, min_xyz, vols = _nb_sample_common(pts, R, T, min_xyz, vols, n_rows)
+    N = pts.shape[0]
+    D, H, W = _nb_dims(out_sh)
+    if grad.dtype != torch.float32 or grad.dim() != 2 or grad.shape[0] != N or grad.shape[1] < NB_FEATURES:
+        raise _lib.XrError('nb_sample_backward: grad must be float32 [N, >= 352]')
+    if N and (grad.stride(1) != 1 or grad.stride(0) % 4 or grad.data_ptr() % 16):
+        grad = grad.contiguous()
+    if not _on_device(grad):
+        _ptr(grad)
+    dev = pts.device
+    outs = [torch.empty((int(n), c), dtype=torch.float32, device=dev) for n, c in zip(n_rows, NB_LEVEL_CHANNELS)]
+    counts = (C.c_uint32 * 4)(*[int(n) for n in n_rows])
+    lib = _lib.load()
+    ws = _ws(dev, int(lib.xr_nb_sample_backward_workspace_bytes(C.cast(counts, C.c_void_p))), 'nb_sample_bwd')
+    with _span('xr_nb_sample_backward', N):
+        _lib.check(lib.xr_nb_sample_backward(_ptr(pts), _ptr(R), _ptr(T), _ptr(min_xyz), float(voxel), D, H, W,
+                                             C.cast(_nb_ptr4(vols), C.c_void_p), C.cast(counts, C.c_void_p), C.c_void_p(grad.data_ptr()),
+                                             grad.stride(0) if N else NB_FEATURES, N, C.cast(_nb_ptr4(outs), C.c_void_p),
+                                             C.c_void_p(ws.data_ptr()), ws.numel(), _stream()), 'xr_nb_sample_backward')
+    return outs
