@@ -209,6 +209,16 @@ NEURALBODY_SIGNATURES = {
     'xr_nb_sample_backward': (_i32, [_vp, _vp, _vp, _vp, _f, _i32, _i32, _i32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _sz, _vp]),
 }
 
+# GNR body-shape queries (csrc/xr_gnr.hip, declared in include/xrnerf_mi355_gnr.h): a table of its own as well
+_GNR_GRID = [_vp, _vp, _u32, _u32, _f, _vp, _vp]          # verts, faces, V, F, step, min3 (host), num3 (host)
+GNR_SIGNATURES = {
+    'xr_gnr_grid_count': (_i32, _GNR_GRID + [_vp, _vp, _vp]),
+    'xr_gnr_grid_fill': (_i32, _GNR_GRID + [_vp, _i32, _vp, _vp, _vp]),
+    'xr_gnr_nearest': (_i32, _GNR_GRID + [_vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    'xr_gnr_inside': (_i32, _GNR_GRID + [_vp, _vp, _i32, _vp, _u32, _vp, _vp]),
+    'xr_gnr_shape_embed': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _f, _f, _i32, _i32, _i32, _vp, _u32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -265,7 +275,7 @@ def load():
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
-            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()):
+            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -42,6 +42,11 @@ SOURCES = {
     # NeuralBody stages (sparse structure, 3x3x3 sparse convolution, feature sampling): the sampling coordinates ((c + 1) / 2) (size - 1)
     # and the trilinear weights must round like torch's grid_sample, whose corner decision is a floorf of them
     'xr_neuralbody.hip': ['-ffp-contract=off'],
+    # GNR body-shape queries (mesh grid, closest point, inside test, embedding): cell decisions are floors of (x - min) / step and the
+    # closest-point solve ranks candidates with strict `<`, so every product and sum must round like the reference's un-fused fp32
+    # (-simplifycfg-sink-common=false, as for xr_scatter.hip: sinking the arms of `if (pivot == 1) swap(a0, a1) else if ...` into one
+    # block leaves a select between element ADDRESSES, which turns the solve's per-thread matrices into scratch memory)
+    'xr_gnr.hip': ['-ffp-contract=off', '-mllvm', '-simplifycfg-sink-common=false'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

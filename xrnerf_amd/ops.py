@@ -2017,3 +2017,96 @@ def nb_sample_backward(pts, R, T, min_xyz, voxel, out_sh, vols, n_rows, grad):
                                              grad.stride(0) if N else NB_FEATURES, N, C.cast(_nb_ptr4(outs), C.c_void_p),
                                              C.c_void_p(ws.data_ptr()), ws.numel(), _stream()), 'xr_nb_sample_backward')
     return outs
+
+
+# ---------------------------------------------------------------- GNR body-shape queries (configs/gnr/gnr_genebody.py)
+GNR_MAX_CELLS = 1 << 28         # XR_GNR_MAX_CELLS
+GNR_EMBED_COLS = 10             # XR_GNR_EMBED_COLS
+
+
+def gnr_kernels_available():
+    """the loaded library handle has xr_gnr.hip's entry points (a handle made of the host builds of other sources may not: gnr.py then
+    keeps its host path)"""
+    return hasattr(_lib.load(), 'xr_gnr_nearest')
+
+
+def _gnr_grid_args(verts, faces, step, min3, num3):
+    """the seven leading arguments of the grid entry points; min3 / num3 are HOST values (kept alive by the returned tuple)"""
+    verts, faces = _f32c(verts).reshape(-1, 3), _i32c(faces).reshape(-1, 3)
+    mn = (C.c_float * 3)(*[float(v) for v in min3])
+    nm = (C.c_int32 * 3)(*[int(v) for v in num3[:3]])
+    return (_ptr(verts), _ptr(faces), verts.shape[0], faces.shape[0], float(step), C.cast(mn, C.c_void_p), C.cast(nm, C.c_void_p)), (verts, faces, mn, nm)
+
+
+def gnr_grid_build(verts, faces, step, min3, num3):
+    """-> (tri_num [cells] int32 inclusive prefix counts, tri_idx [total] int32 face id + 1, bad) with ONE blocking read (the slot total
+    and the face-index flag together); bad: some face names a vertex outside [0, V)"""
+    dev = verts.device
+    cells = int(num3[0]) * int(num3[1]) * int(num3[2])
+    args, keep = _gnr_grid_args(verts, faces, step, min3, num3)
+    lib = _lib.load()
+    tri_num = torch.empty((cells,), dtype=torch.int32, device=dev)
+    status = torch.empty((2,), dtype=torch.int32, device=dev)
+    with _span('xr_gnr_grid_count', args[3]):
+        _lib.check(lib.xr_gnr_grid_count(*args, _ptr(tri_num), _ptr(status), _stream()), 'xr_gnr_grid_count')
+    tri_num = torch.cumsum(tri_num, 0, dtype=torch.int32)
+    status[0:1] = tri_num[-1:]
+    total, bad = status.tolist()
+    tri_idx = torch.empty((total,), dtype=torch.int32, device=dev)
+    if total > 0 and not bad:
+        cursor = _ws(dev, cells * 4, 'gnr_cursor')
+        with _span('xr_gnr_grid_fill', args[3]):
+            _lib.check(lib.xr_gnr_grid_fill(*args, _ptr(tri_num), total, _ptr(tri_idx), C.c_void_p(cursor.data_ptr()), _stream()),
+                       'xr_gnr_grid_fill')
+    return tri_num, tri_idx, bool(bad)
+
+
+def gnr_nearest(verts, faces, step, min3, num3, tri_num, tri_idx, pts):
+    """-> (near_faces [N] int32, near_pts [N,3], coeff [N,3])"""
+    pts = _f32c(pts).reshape(-1, 3)
+    N, dev = pts.shape[0], pts.device
+    args, keep = _gnr_grid_args(verts, faces, step, min3, num3)
+    near_faces = torch.empty((N,), dtype=torch.int32, device=dev)
+    near_pts = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    coeff = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    with _span('xr_gnr_nearest', N):
+        _lib.check(_lib.load().xr_gnr_nearest(*args, _ptr(_i32c(tri_num)), _ptr(_i32c(tri_idx)), tri_idx.numel(), _ptr(pts), N,
+                                              _ptr(near_faces), _ptr(near_pts), _ptr(coeff), _stream()), 'xr_gnr_nearest')
+    return near_faces, near_pts, coeff
+
+
+def gnr_inside(verts, faces, step, min3, num3, tri_num, tri_idx, pts):
+    """-> signs [N] float32 (+1 inside, -1 outside)"""
+    pts = _f32c(pts).reshape(-1, 3)
+    N = pts.shape[0]
+    args, keep = _gnr_grid_args(verts, faces, step, min3, num3)
+    signs = torch.empty((N,), dtype=torch.float32, device=pts.device)
+    with _span('xr_gnr_inside', N):
+        _lib.check(_lib.load().xr_gnr_inside(*args, _ptr(_i32c(tri_num)), _ptr(_i32c(tri_idx)), tri_idx.numel(), _ptr(pts), N, _ptr(signs),
+                                             _stream()), 'xr_gnr_inside')
+    return signs
+
+
+def gnr_shape_embed(pts, near_faces, near_pts, signs, faces, t_verts, center3, rot9, scale, half, use_nml, use_t_pose, use_smpl_sdf):
+    """the embedding half of make_nerf_input -> (out [N, 3 + 3 use_t_pose + 4 use_smpl_sdf], alpha_smpl [N] or None); center3 [3] / rot9 [3,3]
+    are device tensors"""
+    pts = _f32c(pts).reshape(-1, 3)
+    N, dev = pts.shape[0], pts.device
+    cols = 3 + (3 if use_t_pose else 0) + (4 if use_smpl_sdf else 0)
+    out = torch.empty((N, cols), dtype=torch.float32, device=dev)
+    alpha = torch.empty((N,), dtype=torch.float32, device=dev) if use_smpl_sdf else None
+    c3 = _f32c(center3).reshape(3) if center3 is not None else None
+    r9 = _f32c(rot9).reshape(9) if rot9 is not None else None
+    F = V = 0
+    if use_t_pose:
+        faces, t_verts, near_faces = _i32c(faces).reshape(-1, 3), _f32c(t_verts).reshape(-1, 3), _i32c(near_faces)
+        F, V = faces.shape[0], t_verts.shape[0]
+    if use_smpl_sdf:
+        near_pts, signs = _f32c(near_pts).reshape(-1, 3), _f32c(signs)
+    with _span('xr_gnr_shape_embed', N):
+        _lib.check(_lib.load().xr_gnr_shape_embed(
+            _ptr(pts), N, _ptr(near_faces) if use_t_pose else None, _ptr(near_pts) if use_smpl_sdf else None,
+            _ptr(signs) if use_smpl_sdf else None, _ptr(faces) if use_t_pose else None, F, _ptr(t_verts) if use_t_pose else None, V,
+            _ptr(c3), _ptr(r9), float(scale), float(half),
+            int(bool(use_nml)), int(bool(use_t_pose)), int(bool(use_smpl_sdf)), _ptr(out), cols, _ptr(alpha), _stream()), 'xr_gnr_shape_embed')
+    return out, alpha
