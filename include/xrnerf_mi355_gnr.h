@@ -25,6 +25,7 @@ extern "C" {
 #define XR_GNR_MAX_CELLS (1u << 28)
 #define XR_GNR_VISITED 16            /* the inside test's buffer: entry 0 unused, 15 face ids */
 #define XR_GNR_EMBED_COLS 10         /* 3 normalised point + 3 T-pose + 3 SDF direction + 1 SDF */
+#define XR_GNR_MAX_VIEWS 8           /* source views of the renderer's stages */
 
 /* first pass: tri_num [cells] = the number of slots of every cell (cleared here), one thread per face, integer atomic adds.
  * status [2] (cleared here): status[1] becomes 1 when a face names a vertex outside [0, V); such a face is left out of both passes.
@@ -54,6 +55,55 @@ int xr_gnr_shape_embed(const float* pts, uint32_t N, const int32_t* near_faces, 
                        const int32_t* faces, uint32_t F, const float* t_verts, uint32_t V, const float* center3, const float* rot9,
                        float scale, float half, int use_nml, int use_t_pose, int use_smpl_sdf, float* out, uint32_t ld, float* alpha,
                        void* stream);
+
+/* ---- the renderer's stages (xrnerf_amd/csrc/xr_gnr_render.hip): what GnrRenderer.render_rays does around the network ----
+ * R rays of S samples, V <= XR_GNR_MAX_VIEWS source views.  rays [R,6] = (start, end); t_vals [R,S]; the sample point is
+ * end t + (1 - t) start.  w2c [V,4,4] row-major; cams [V,cam_cols] = fx, fy, cx, cy, then (cam_cols > 6) k1, k2, p1, p2, k3 at
+ * entries 4 .. 8; masks [V,H,W]; width / height = what the pixel coordinates are divided by (loadSize).  A point is inside when, in
+ * every view, torch's grid_sample(mode='nearest', align_corners=False, zero padding) of the mask at its projection is > 0; a point
+ * with a non-finite projected coordinate is outside (torch leaves that case unspecified). */
+
+/* count / scan: rank [R S] (workspace: a survivor's rank inside its ray, -1 otherwise), table [R,2] = (count, base) per ray,
+ * total [1] = M.  Three launches; the caller reads total ONCE to size the next call's outputs.  R = 0 clears total. */
+int xr_gnr_hull_count(const float* rays, const float* t_vals, uint32_t R, uint32_t S, const float* w2c, const float* cams,
+                      uint32_t cam_cols, uint32_t V, const float* masks, int H, int W, float width, float height, int32_t* rank,
+                      int32_t* table, int32_t* total, void* stream);
+/* ranked write, survivors in ascending flat index (the order of torch.nonzero): pts [M,3], idx [M] (flat index r S + s), xy [M,V,2]
+ * (normalised), z [M,V] (camera depth); with depth [V,H,W] (smpl['depth'], nearest sample d): vis [M,V] bytes = (z - d <= 0) & (d > 0);
+ * with attdirs [M,V+1,3]: make_att_input's perspective branch -- [start - end | cam_c [V,3] - point], each times rot9 (row vector
+ * times the row-major matrix; may be null), over clamp(norm, 1e-9).  depth, vis, attdirs, cam_c, rot9 may be null.  M = 0: no-op. */
+int xr_gnr_hull_write(const float* rays, const float* t_vals, uint32_t R, uint32_t S, const float* w2c, const float* cams,
+                      uint32_t cam_cols, uint32_t V, const float* masks, const float* depth, int H, int W, float width, float height,
+                      const float* cam_c, const float* rot9, const int32_t* rank, const int32_t* table, uint32_t M, float* pts,
+                      int32_t* idx, float* xy, float* z, uint8_t* vis, float* attdirs, void* stream);
+/* pixel-aligned gather (the `feats is not None` half of make_nerf_input): bilinear samples, torch's grid_sample defaults
+ * (align_corners=False, zero padding), its corner order and weight products.  feats [V,fh,fw,C] CHANNEL-LAST, C a multiple of 4,
+ * 16-byte aligned; images [V,3,ih,iw], or [V,ih,iw,3] with images_channel_last.  Row (m V + v) of out starts at out + (m V + v) ld:
+ * columns col0 .. col0 + C hold the features, the next 3 the sampled colour, the rest up to ld exact zeros; columns below col0 are
+ * left alone.  source_rgb [M,V,3] holds the sampled colours again. */
+int xr_gnr_gather(const float* xy, uint32_t M, uint32_t V, const float* feats, int fh, int fw, uint32_t C, const float* images, int ih,
+                  int iw, int images_channel_last, float* out, uint32_t ld, uint32_t col0, float* source_rgb, void* stream);
+/* the gather's gradient in the feature maps (needed when the encoder is trained): d_feats [V,fh,fw,C] channel-last, every element
+ * written, from grad rows laid out like xr_gnr_gather's out (columns col0 .. col0 + C are read; the colour columns have no trained
+ * source).  64-bit fixed point: the largest |grad|, one scale for the call, integer atomic adds, one conversion -- two runs give the
+ * same bits; a NaN or infinite entry contributes nothing.  Four launches and a clear of the workspace (8-byte aligned, at least
+ * xr_gnr_gather_backward_workspace_bytes). */
+size_t xr_gnr_gather_backward_workspace_bytes(uint32_t V, int fh, int fw, uint32_t C);
+int xr_gnr_gather_backward(const float* xy, uint32_t M, uint32_t V, const float* grad, uint32_t ld, uint32_t col0, int fh, int fw,
+                           uint32_t C, float* d_feats, void* workspace, size_t workspace_bytes, void* stream);
+/* blend compositor (make_nerf_output and the lines around it), one wave per ray, the ray's survivors in its lanes in sample order.  net [M,ld]:
+ * columns 0 .. 2 colour, 3 density, 4 .. 4 + V attention over [own colour | V source colours]; source_rgb [M,V,3]; idx / table as
+ * written by the hull; noise [R,S] is added to the density (null: inference).  alpha = 1 - exp(-relu(.)) uses no distances, the
+ * transmittance is the running product of (1 - alpha) + 1e-10.  rgb_map [R,6], depth [R] over z = t z_near + (1 - t) z_far (have_z)
+ * or 2 t - 1, acc [R], weights [R,S] (cleared here: zeros outside the hull), trans [M] (kept for the backward).  white: rgb_map + (1 - acc). */
+int xr_gnr_composite_forward(const float* net, uint32_t ld, const float* source_rgb, const int32_t* idx, const int32_t* table,
+                             const float* t_vals, const float* noise, uint32_t R, uint32_t S, uint32_t V, uint32_t M, int have_z,
+                             float z_near, float z_far, int white, float* rgb_map, float* depth, float* acc, float* weights,
+                             float* trans, void* stream);
+/* d_net [M, 4 + V + 1] (every entry written) from d_rgb_map [R,6]; fixed summation order, no atomics */
+int xr_gnr_composite_backward(const float* net, uint32_t ld, const float* source_rgb, const int32_t* idx, const int32_t* table,
+                              const float* t_vals, const float* noise, uint32_t R, uint32_t S, uint32_t V, uint32_t M, int white,
+                              const float* d_rgb_map, const float* trans, float* d_net, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,6 @@ vanilla-NeRF (config #1, `vanilla.py`), Mip-NeRF (config #3, `mip.py`) and KiloN
 """
 from . import builder  # noqa: F401
 from .builder import build_embedder, build_mlp, build_network, build_render, build_sampler  # noqa: F401
-from . import mlps, networks, renders, samplers, vanilla, mip, kilo, kilo_distill, bungee, aninerf, neuralbody, gnr  # noqa: F401,E402
+from . import mlps, networks, renders, samplers, vanilla, mip, kilo, kilo_distill, bungee, aninerf, neuralbody, gnr, gnr_render  # noqa: F401,E402
 
 __version__ = '0.1.0'

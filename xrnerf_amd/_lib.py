@@ -219,6 +219,19 @@ GNR_SIGNATURES = {
     'xr_gnr_shape_embed': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _f, _f, _i32, _i32, _i32, _vp, _u32, _vp, _vp]),
 }
 
+# GNR renderer stages (csrc/xr_gnr_render.hip, declared in include/xrnerf_mi355_gnr.h as well): a table of its own, like every family's
+GNR_RENDER_SIGNATURES = {
+    'xr_gnr_hull_count': (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _vp, _i32, _i32, _f, _f, _vp, _vp, _vp, _vp]),
+    'xr_gnr_hull_write': (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _i32, _i32, _f, _f, _vp, _vp, _vp, _vp, _u32, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp]),
+    'xr_gnr_gather': (_i32, [_vp, _u32, _u32, _vp, _i32, _i32, _u32, _vp, _i32, _i32, _i32, _vp, _u32, _u32, _vp, _vp]),
+    'xr_gnr_gather_backward_workspace_bytes': (_sz, [_u32, _i32, _i32, _u32]),
+    'xr_gnr_gather_backward': (_i32, [_vp, _u32, _u32, _vp, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _sz, _vp]),
+    'xr_gnr_composite_forward': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _f, _f, _i32, _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    'xr_gnr_composite_backward': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -275,7 +288,7 @@ def load():
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
-            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()):
+            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -47,6 +47,10 @@ SOURCES = {
     # (-simplifycfg-sink-common=false, as for xr_scatter.hip: sinking the arms of `if (pivot == 1) swap(a0, a1) else if ...` into one
     # block leaves a select between element ADDRESSES, which turns the solve's per-thread matrices into scratch memory)
     'xr_gnr.hip': ['-ffp-contract=off', '-mllvm', '-simplifycfg-sink-common=false'],
+    # GNR renderer stages (visual hull, pixel-aligned gather, blend compositor): the hull's decision is a rounding to the nearest mask
+    # pixel of a projected coordinate and the gather's corner a floorf of one, so the projection must round like its un-fused fp32
+    # tensor-op restatement
+    'xr_gnr_render.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

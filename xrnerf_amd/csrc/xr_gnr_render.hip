@@ -1,0 +1,621 @@
+// GNR's renderer stages (configs/gnr/gnr_genebody.py) for gfx950: what GnrRenderer.render_rays does around the network, as kernels.
+// The reference's tensor lines are the specification, quirks included; every expression below is fp32 in the
+// reference's order, compiled with -ffp-contract=off.
+//   k_gr_flag      thread = (ray, sample): the sample point, its projection into every source view (w2c, division by clamp(z, 1e-9),
+//                  five-coefficient distortion, intrinsics, normalisation) and the nearest mask sample of torch's grid_sample
+//   k_gr_ray       thread = ray: the ray's flags become ranks inside the ray, their number the ray's count
+//   k_gr_scan      one workgroup: exclusive scan of the counts -> (count, base) per ray and the total
+//   k_gr_write     thread = (ray, sample): a survivor writes its row at base + rank -- ascending flat index, the order of
+//                  torch.nonzero -- with what the later stages need, so nothing is projected a second time
+//   k_gr_gather    thread = (survivor, view, float4 of channels): bilinear samples of the channel-last feature maps and of the
+//                  images, written at a row stride into the network's input
+//   k_gr_gather_bwd  the same walk, adding w g to the feature maps in 64-bit fixed point (k_gr_absmax, k_gr_scale, k_gr_gather_cvt around it)
+//   k_gr_comp_fwd  wave = ray, lane = survivor, 64 at a time in sample order (outside the hull the reference's -1e4 gives alpha = 0
+//                  and a factor of exactly 1.0f, so leaving those samples out changes no factor of the running product); the
+//                  transmittance is a product scan over the lanes, the sums a butterfly: a fixed order, the same bits every run
+//   k_gr_comp_bwd  wave = ray, the chunks backwards with a suffix scan of B <- G alpha + (1 - alpha + 1e-10) B; no division by a
+//                  transmittance, no atomics
+#include "xr_common.h"
+#include "../../include/xrnerf_mi355_gnr.h"
+
+#define GR_BLOCK 256
+#define GR_WAVES (GR_BLOCK / 64)
+#define GR_V XR_GNR_MAX_VIEWS
+
+struct GrHull {
+    const float* rays; const float* t_vals; uint32_t R, S, V;
+    const float* w2c; const float* cams; uint32_t cam_cols;
+    const float* masks; const float* depth; int H, W;
+    float width, height;
+    const float* cam_c; const float* rot;
+};
+
+// camera-space point of view v, sum_k ascending, then the translation
+static __device__ inline void gr_camera(const GrHull& a, uint32_t v, const float* p, float* c) {
+    const float* m = a.w2c + 16ull * v;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = ((m[4 * j] * p[0] + m[4 * j + 1] * p[1]) + m[4 * j + 2] * p[2]) + m[4 * j + 3];
+}
+
+// perspective() and the normalisation to [-1, 1]: xy[2], and the depth c[2] comes back in *z
+static __device__ inline void gr_project(const GrHull& a, uint32_t v, const float* p, float* xy, float* z) {
+    float c[3];
+    gr_camera(a, v, p, c);
+    const float zc = c[2] < 1e-9f ? 1e-9f : c[2];                  // (a NaN depth stays NaN: no comparison holds)
+    float x = c[0] / zc, y = c[1] / zc;
+    const float* cam = a.cams + (uint64_t)v * a.cam_cols;
+    if (a.cam_cols > 6) {
+        const float x2 = x * x, y2 = y * y, xy_ = x * y, r2 = x2 + y2;
+        const float k = 1.f + r2 * (cam[4] + r2 * (cam[5] + r2 * cam[8]));
+        const float dx = cam[6] * 2.f * xy_ + cam[7] * (r2 + 2.f * x2);
+        const float dy = cam[7] * 2.f * xy_ + cam[6] * (r2 + 2.f * y2);
+        x = k * x + dx;
+        y = k * y + dy;
+    }
+    x = cam[0] * x + cam[2];
+    y = cam[1] * y + cam[3];
+    xy[0] = x / a.width * 2.f - 1.f;
+    xy[1] = y / a.height * 2.f - 1.f;
+    *z = c[2];
+}
+
+static __device__ inline bool gr_finite(float x) { return x - x == 0.f; }
+
+// grid_sample(mode='nearest', align_corners=False, zero padding): the source pixel of a normalised coordinate, or false
+static __device__ inline bool gr_nearest_pixel(float nx, float ny, int H, int W, int* px, int* py) {
+    if (!gr_finite(nx) || !gr_finite(ny)) return false;
+    const float fx = rintf(((nx + 1.f) * (float)W - 1.f) / 2.f), fy = rintf(((ny + 1.f) * (float)H - 1.f) / 2.f);
+    if (!(fx >= 0.f && fx <= (float)(W - 1) && fy >= 0.f && fy <= (float)(H - 1))) return false;
+    *px = (int)fx; *py = (int)fy;
+    return true;
+}
+
+static __device__ inline void gr_point(const GrHull& a, uint32_t r, uint32_t s, float* p) {
+    const float t = a.t_vals[(uint64_t)r * a.S + s];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = a.rays[6ull * r + 3 + c] * t + (1.f - t) * a.rays[6ull * r + c];
+}
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_flag(GrHull a, int32_t* __restrict__ rank) {
+    const uint64_t id = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
+    if (id >= (uint64_t)a.R * a.S) return;
+    const uint32_t r = (uint32_t)(id / a.S), s = (uint32_t)(id - (uint64_t)r * a.S);
+    float p[3];
+    gr_point(a, r, s, p);
+    bool in = true;
+    for (uint32_t v = 0; v < a.V; ++v) {
+        float xy[2], z;
+        int px, py;
+        gr_project(a, v, p, xy, &z);
+        if (!gr_nearest_pixel(xy[0], xy[1], a.H, a.W, &px, &py)) { in = false; break; }
+        if (!(a.masks[((uint64_t)v * a.H + py) * a.W + px] > 0.f)) { in = false; break; }
+    }
+    rank[id] = in ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_ray(uint32_t R, uint32_t S, int32_t* __restrict__ rank, int32_t* __restrict__ table) {
+    const uint32_t r = blockIdx.x * GR_BLOCK + threadIdx.x;
+    if (r >= R) return;
+    int32_t* row = rank + (uint64_t)r * S;
+    int32_t n = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const int32_t f = row[s];
+        row[s] = f ? n : -1;
+        n += f;
+    }
+    table[2ull * r] = n;
+}
+
+// exclusive scan of table[r][0] -> table[r][1], the total -> total[0]; one workgroup, 256 rays per sweep (k_nb_scan's pattern)
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_scan(uint32_t R, int32_t* __restrict__ table, int32_t* __restrict__ total) {
+    __shared__ uint32_t s_w[GR_WAVES];
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < R; b0 += GR_BLOCK) {
+        const uint32_t b = b0 + t;
+        const uint32_t c = b < R ? (uint32_t)table[2ull * b] : 0u;
+        uint32_t incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t v = __shfl_up(incl, o, 64);
+            if ((int)lane >= o) incl += v;
+        }
+        __syncthreads();                                           // s_w of the previous sweep has been read
+        if (lane == 63) s_w[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, sum = 0;
+        for (uint32_t w = 0; w < GR_WAVES; ++w) { if (w < wave) before += s_w[w]; sum += s_w[w]; }
+        if (b < R) table[2ull * b + 1] = (int32_t)(carry + before + incl - c);
+        carry += sum;
+    }
+    if (t == 0) total[0] = (int32_t)carry;
+}
+
+struct GrRows {
+    uint32_t M;
+    float* pts; int32_t* idx; float* xy; float* z; uint8_t* vis; float* attdirs;
+};
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_write(GrHull a, const int32_t* __restrict__ rank, const int32_t* __restrict__ table, GrRows o) {
+    const uint64_t id = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
+    if (id >= (uint64_t)a.R * a.S) return;
+    const int32_t k = rank[id];
+    if (k < 0) return;
+    const uint32_t r = (uint32_t)(id / a.S), s = (uint32_t)(id - (uint64_t)r * a.S);
+    const uint64_t m = (uint64_t)(uint32_t)table[2ull * r + 1] + (uint32_t)k;
+    if (m >= o.M) return;                                          // (the caller's M is the scan's total: never taken)
+    float p[3];
+    gr_point(a, r, s, p);
+    o.pts[3 * m] = p[0]; o.pts[3 * m + 1] = p[1]; o.pts[3 * m + 2] = p[2];
+    o.idx[m] = (int32_t)id;
+    for (uint32_t v = 0; v < a.V; ++v) {
+        float xy[2], z;
+        gr_project(a, v, p, xy, &z);
+        o.xy[(m * a.V + v) * 2] = xy[0]; o.xy[(m * a.V + v) * 2 + 1] = xy[1];
+        o.z[m * a.V + v] = z;
+        if (a.depth) {
+            int px, py;
+            float d = 0.f;
+            if (gr_nearest_pixel(xy[0], xy[1], a.H, a.W, &px, &py)) d = a.depth[((uint64_t)v * a.H + py) * a.W + px];
+            o.vis[m * a.V + v] = (z - d <= 0.f && d > 0.f) ? 1 : 0;
+        }
+    }
+    if (o.attdirs) {
+        // make_att_input, perspective branch: [query direction | camera centres - point], through rot, over clamp(norm, 1e-9)
+        float rot[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) rot[c] = a.rot ? a.rot[c] : ((c == 0 || c == 4 || c == 8) ? 1.f : 0.f);
+        for (uint32_t v = 0; v <= a.V; ++v) {
+            float d[3], y[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                d[c] = v == 0 ? a.rays[6ull * r + c] - a.rays[6ull * r + 3 + c] : a.cam_c[3ull * (v - 1) + c] - p[c];
+            if (a.rot) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) y[j] = (d[0] * rot[j] + d[1] * rot[3 + j]) + d[2] * rot[6 + j];
+            } else { y[0] = d[0]; y[1] = d[1]; y[2] = d[2]; }
+            float n = sqrtf((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2]);
+            if (n < 1e-9f) n = 1e-9f;
+            float* q = o.attdirs + (m * (a.V + 1) + v) * 3;
+            q[0] = y[0] / n; q[1] = y[1] / n; q[2] = y[2] / n;
+        }
+    }
+}
+
+static int gr_hull_args(GrHull* a, const char* fn, const float* rays, const float* t_vals, uint32_t R, uint32_t S, const float* w2c,
+                        const float* cams, uint32_t cam_cols, uint32_t V, const float* masks, int H, int W, float width, float height) {
+    if (!rays || !t_vals || !w2c || !cams || !masks) { xr_set_error("%s: null pointer", fn); return XR_EINVAL; }
+    if (V < 1 || V > GR_V) { xr_set_error("%s: 1 .. XR_GNR_MAX_VIEWS source views", fn); return XR_EINVAL; }
+    if (cam_cols < 4 || (cam_cols > 6 && cam_cols < 9)) { xr_set_error("%s: a camera row has 4 .. 6 entries, or at least 9 with distortion", fn); return XR_EINVAL; }
+    if (H < 1 || W < 1 || H > (1 << 14) || W > (1 << 14)) { xr_set_error("%s: bad mask size", fn); return XR_EINVAL; }
+    if (!(width > 0.f) || !(height > 0.f)) { xr_set_error("%s: the image size must be positive", fn); return XR_EINVAL; }
+    if (S < 1 || (uint64_t)R * S > (1ull << 30)) { xr_set_error("%s: bad ray or sample count", fn); return XR_EINVAL; }
+    memset(a, 0, sizeof(*a));
+    a->rays = rays; a->t_vals = t_vals; a->R = R; a->S = S; a->V = V; a->w2c = w2c; a->cams = cams; a->cam_cols = cam_cols;
+    a->masks = masks; a->H = H; a->W = W; a->width = width; a->height = height;
+    return 0;
+}
+
+extern "C" int xr_gnr_hull_count(const float* rays, const float* t_vals, uint32_t R, uint32_t S, const float* w2c, const float* cams,
+                                 uint32_t cam_cols, uint32_t V, const float* masks, int H, int W, float width, float height, int32_t* rank,
+                                 int32_t* table, int32_t* total, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    XR_REQUIRE(total != nullptr, "null pointer");
+    if (R == 0) { XR_HIP(hipMemsetAsync(total, 0, sizeof(int32_t), st)); return 0; }
+    GrHull a;
+    const int rc = gr_hull_args(&a, __func__, rays, t_vals, R, S, w2c, cams, cam_cols, V, masks, H, W, width, height);
+    if (rc != 0) return rc;
+    XR_REQUIRE(rank && table, "null pointer");
+    hipLaunchKernelGGL(k_gr_flag, dim3(xr_div_up((uint64_t)R * S, GR_BLOCK)), dim3(GR_BLOCK), 0, st, a, rank);
+    hipLaunchKernelGGL(k_gr_ray, dim3(xr_div_up(R, GR_BLOCK)), dim3(GR_BLOCK), 0, st, R, S, rank, table);
+    hipLaunchKernelGGL(k_gr_scan, dim3(1), dim3(GR_BLOCK), 0, st, R, table, total);
+    XR_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int xr_gnr_hull_write(const float* rays, const float* t_vals, uint32_t R, uint32_t S, const float* w2c, const float* cams,
+                                 uint32_t cam_cols, uint32_t V, const float* masks, const float* depth, int H, int W, float width, float height,
+                                 const float* cam_c, const float* rot9, const int32_t* rank, const int32_t* table, uint32_t M, float* pts,
+                                 int32_t* idx, float* xy, float* z, uint8_t* vis, float* attdirs, void* stream) {
+    if (R == 0 || M == 0) return 0;
+    GrHull a;
+    const int rc = gr_hull_args(&a, __func__, rays, t_vals, R, S, w2c, cams, cam_cols, V, masks, H, W, width, height);
+    if (rc != 0) return rc;
+    XR_REQUIRE(rank && table && pts && idx && xy && z, "null pointer");
+    XR_REQUIRE((uint64_t)M <= (uint64_t)R * S, "more survivors than points");
+    XR_REQUIRE(!depth || vis, "the depth maps need the visibility output");
+    XR_REQUIRE(!attdirs || cam_c, "the attention directions need the camera centres");
+    a.depth = depth; a.cam_c = cam_c; a.rot = rot9;
+    GrRows o;
+    o.M = M; o.pts = pts; o.idx = idx; o.xy = xy; o.z = z; o.vis = vis; o.attdirs = attdirs;
+    hipLaunchKernelGGL(k_gr_write, dim3(xr_div_up((uint64_t)R * S, GR_BLOCK)), dim3(GR_BLOCK), 0, (hipStream_t)stream, a, rank, table, o);
+    XR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ pixel-aligned gather
+struct GrGather {
+    const float* xy; uint32_t M, V;
+    const float* feats; int fh, fw; uint32_t C;          // [V, fh, fw, C] channel-last, C a multiple of 4
+    const float* images; int ih, iw; int images_last;    // [V, 3, ih, iw], or [V, ih, iw, 3]
+    float* out; uint32_t ld, col0;                       // row (m V + v) of out, columns col0 .. col0 + C + 3
+    float* source_rgb;                                   // [M, V, 3]
+};
+
+// torch's grid_sampler_compute_source_index + the four corners (nw, ne, sw, se) and their weight products
+struct GrCorners { int x0, y0; float w[4]; };
+static __device__ inline void gr_corners(float nx, float ny, int H, int W, GrCorners* c) {
+    const float ix = ((nx + 1.f) * (float)W - 1.f) / 2.f, iy = ((ny + 1.f) * (float)H - 1.f) / 2.f;
+    const float fx = floorf(ix), fy = floorf(iy);
+    // a coordinate beyond the map by more than a pixel (or not finite) has no corner inside: park it so the int conversion is defined
+    const bool far = !(fx >= -2.f && fx <= (float)W && fy >= -2.f && fy <= (float)H);
+    c->x0 = far ? -2 : (int)fx; c->y0 = far ? -2 : (int)fy;
+    const float x1 = fx + 1.f, y1 = fy + 1.f;
+    c->w[0] = (x1 - ix) * (y1 - iy);
+    c->w[1] = (ix - fx) * (y1 - iy);
+    c->w[2] = (x1 - ix) * (iy - fy);
+    c->w[3] = (ix - fx) * (iy - fy);
+}
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_gather(GrGather a) {
+    const uint32_t q4 = a.C / 4, per = q4 + 1;                    // the last slot of a (survivor, view) samples the image
+    const uint64_t id = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
+    if (id >= (uint64_t)a.M * a.V * per) return;
+    const uint64_t mv = id / per;
+    const uint32_t q = (uint32_t)(id - mv * per), v = (uint32_t)(mv % a.V);
+    const float nx = a.xy[2 * mv], ny = a.xy[2 * mv + 1];
+    float* row = a.out + mv * a.ld + a.col0;
+    GrCorners c;
+    if (q < q4) {
+        gr_corners(nx, ny, a.fh, a.fw, &c);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = c.x0 + (k & 1), y = c.y0 + (k >> 1);
+            if (x >= 0 && x < a.fw && y >= 0 && y < a.fh) {
+                const float4 f = *reinterpret_cast<const float4*>(a.feats + (((uint64_t)v * a.fh + y) * a.fw + x) * a.C + 4ull * q);
+                acc.x += f.x * c.w[k]; acc.y += f.y * c.w[k]; acc.z += f.z * c.w[k]; acc.w += f.w * c.w[k];
+            }
+        }
+        row[4 * q] = acc.x; row[4 * q + 1] = acc.y; row[4 * q + 2] = acc.z; row[4 * q + 3] = acc.w;
+    } else {
+        gr_corners(nx, ny, a.ih, a.iw, &c);
+        float rgb[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = c.x0 + (k & 1), y = c.y0 + (k >> 1);
+            if (x >= 0 && x < a.iw && y >= 0 && y < a.ih) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const uint64_t at = a.images_last ? (((uint64_t)v * a.ih + y) * a.iw + x) * 3 + ch
+                                                      : (((uint64_t)v * 3 + ch) * a.ih + y) * a.iw + x;
+                    rgb[ch] += a.images[at] * c.w[k];
+                }
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) { row[a.C + ch] = rgb[ch]; a.source_rgb[3 * mv + ch] = rgb[ch]; }
+        for (uint32_t p = a.col0 + a.C + 3; p < a.ld; ++p) a.out[mv * a.ld + p] = 0.f;           // the padding columns
+    }
+}
+
+extern "C" int xr_gnr_gather(const float* xy, uint32_t M, uint32_t V, const float* feats, int fh, int fw, uint32_t C, const float* images,
+                             int ih, int iw, int images_channel_last, float* out, uint32_t ld, uint32_t col0, float* source_rgb, void* stream) {
+    if (M == 0) return 0;
+    XR_REQUIRE(xy && feats && images && out && source_rgb, "null pointer");
+    XR_REQUIRE(V >= 1 && V <= GR_V, "1 .. XR_GNR_MAX_VIEWS source views");
+    XR_REQUIRE(M <= (1u << 28), "too many points");
+    XR_REQUIRE(C >= 4 && C % 4 == 0 && C <= 4096, "the feature channels must be a multiple of 4");
+    XR_REQUIRE(fh >= 1 && fw >= 1 && ih >= 1 && iw >= 1 && fh <= (1 << 14) && fw <= (1 << 14) && ih <= (1 << 14) && iw <= (1 << 14), "bad map size");
+    XR_REQUIRE((uint64_t)col0 + C + 3 <= ld, "the row stride is smaller than the row");
+    XR_REQUIRE(((uintptr_t)feats & 15) == 0, "the feature maps must be 16-byte aligned");
+    GrGather a;
+    a.xy = xy; a.M = M; a.V = V; a.feats = feats; a.fh = fh; a.fw = fw; a.C = C; a.images = images; a.ih = ih; a.iw = iw;
+    a.images_last = images_channel_last ? 1 : 0; a.out = out; a.ld = ld; a.col0 = col0; a.source_rgb = source_rgb;
+    const uint64_t n = (uint64_t)M * V * (C / 4 + 1);
+    hipLaunchKernelGGL(k_gr_gather, dim3(xr_div_up(n, GR_BLOCK)), dim3(GR_BLOCK), 0, (hipStream_t)stream, a);
+    XR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- backward: the gradient in the feature maps, 64-bit fixed point (k_nb_sample_bwd's scheme: integer adds commute, so two runs
+// give the same bits)
+#define GR_MAX_BMAX 1024u
+#define GR_BWD_HEAD (GR_MAX_BMAX * sizeof(float) + sizeof(double))
+
+struct GrGatherBwd {
+    const float* xy; uint32_t M, V;
+    const float* grad; uint32_t ld, col0;                // row (m V + v) of grad, columns col0 .. col0 + C
+    int fh, fw; uint32_t C;
+    const double* scale; unsigned long long* acc;        // [V, fh, fw, C]
+};
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_absmax(GrGatherBwd a, float* __restrict__ bmax) {
+    __shared__ float s_m[GR_BLOCK];
+    float m = 0.f;
+    const uint64_t total = (uint64_t)a.M * a.V * a.C;
+    for (uint64_t e = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x; e < total; e += (uint64_t)gridDim.x * GR_BLOCK) {
+        const uint64_t mv = e / a.C;
+        const float g = fabsf(a.grad[mv * a.ld + a.col0 + (uint32_t)(e - mv * a.C)]);
+        if (g <= 3.0e38f) m = fmaxf(m, g);                          // (a NaN or an infinite entry contributes nothing, here either)
+    }
+    s_m[threadIdx.x] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < GR_BLOCK; ++k) m = fmaxf(m, s_m[k]);
+        bmax[blockIdx.x] = m;
+    }
+}
+
+// 2^(61 - b - e) with max |grad| < 2^e and M <= 2^b: a map element receives at most one corner of every (point, view) of its view, each
+// |w g| <= |g|, so its sum stays below 2^61 in magnitude.  ONE workgroup folds the block maxima into the scale, once per call
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_scale(const float* __restrict__ bmax, uint32_t n_bmax, uint32_t n, double* __restrict__ scale) {
+    __shared__ float s_m[GR_BLOCK];
+    float m = 0.f;
+    for (uint32_t e = threadIdx.x; e < n_bmax; e += GR_BLOCK) m = fmaxf(m, bmax[e]);
+    s_m[threadIdx.x] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < GR_BLOCK; ++k) m = fmaxf(m, s_m[k]);
+        int ex = 0, b = 0;
+        if (m > 0.f) frexpf(m, &ex);
+        while (b < 31 && (1u << b) < n) ++b;
+        scale[0] = ldexp(1.0, 61 - b - ex);
+    }
+}
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_gather_bwd(GrGatherBwd a) {
+    const uint32_t q4 = a.C / 4;
+    const uint64_t id = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
+    if (id >= (uint64_t)a.M * a.V * q4) return;
+    const uint64_t mv = id / q4;
+    const uint32_t q = (uint32_t)(id - mv * q4), v = (uint32_t)(mv % a.V);
+    const double scale = a.scale[0];
+    GrCorners c;
+    gr_corners(a.xy[2 * mv], a.xy[2 * mv + 1], a.fh, a.fw, &c);
+    const float* g = a.grad + mv * a.ld + a.col0 + 4u * q;
+    const float ge[4] = {g[0], g[1], g[2], g[3]};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = c.x0 + (k & 1), y = c.y0 + (k >> 1);
+        if (!(x >= 0 && x < a.fw && y >= 0 && y < a.fh)) continue;
+        unsigned long long* d = a.acc + (((uint64_t)v * a.fh + y) * a.fw + x) * a.C + 4ull * q;
+        const double w = (double)c.w[k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double t = (w * (double)ge[j]) * scale;
+            // (a NaN or an infinite gradient contributes nothing: |t| < 2^61 for every finite one, and llrint is undefined beyond 2^63)
+            if (t != 0.0 && fabs(t) < 4.0e18) atomicAdd(d + j, (unsigned long long)(long long)llrint(t));
+        }
+    }
+}
+
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_gather_cvt(const double* __restrict__ scale, const unsigned long long* __restrict__ acc,
+                                                            uint64_t n, float* __restrict__ out) {
+    const uint64_t e = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
+    if (e >= n) return;
+    out[e] = (float)((double)(long long)acc[e] / scale[0]);
+}
+
+extern "C" size_t xr_gnr_gather_backward_workspace_bytes(uint32_t V, int fh, int fw, uint32_t C) {
+    if (fh < 1 || fw < 1) return 0;
+    return (size_t)(GR_BWD_HEAD + (uint64_t)V * (uint32_t)fh * (uint32_t)fw * C * sizeof(unsigned long long));
+}
+
+extern "C" int xr_gnr_gather_backward(const float* xy, uint32_t M, uint32_t V, const float* grad, uint32_t ld, uint32_t col0, int fh, int fw,
+                                      uint32_t C, float* d_feats, void* workspace, size_t workspace_bytes, void* stream) {
+    XR_REQUIRE(d_feats != nullptr, "null pointer");
+    XR_REQUIRE(V >= 1 && V <= GR_V, "1 .. XR_GNR_MAX_VIEWS source views");
+    XR_REQUIRE(M <= (1u << 28), "too many points");
+    XR_REQUIRE(C >= 4 && C % 4 == 0 && C <= 4096, "the feature channels must be a multiple of 4");
+    XR_REQUIRE(fh >= 1 && fw >= 1 && fh <= (1 << 14) && fw <= (1 << 14), "bad map size");
+    XR_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 7u) == 0, "the workspace must be 8-byte aligned");
+    if (workspace_bytes < xr_gnr_gather_backward_workspace_bytes(V, fh, fw, C)) { xr_set_error("%s: workspace too small", __func__); return XR_ENOMEM; }
+    const uint64_t el = (uint64_t)V * (uint32_t)fh * (uint32_t)fw * C;
+    hipStream_t st = (hipStream_t)stream;
+    float* bmax = (float*)workspace;
+    double* scale = (double*)((char*)workspace + GR_MAX_BMAX * sizeof(float));
+    unsigned long long* acc = (unsigned long long*)((char*)workspace + GR_BWD_HEAD);
+    XR_HIP(hipMemsetAsync(workspace, 0, GR_BWD_HEAD + (size_t)el * sizeof(unsigned long long), st));
+    GrGatherBwd a;
+    a.xy = xy; a.M = M; a.V = V; a.grad = grad; a.ld = ld; a.col0 = col0; a.fh = fh; a.fw = fw; a.C = C; a.scale = scale; a.acc = acc;
+    uint32_t nbm = 1;
+    if (M != 0) {
+        XR_REQUIRE(xy && grad, "null pointer");
+        XR_REQUIRE((uint64_t)col0 + C <= ld, "the row stride is smaller than the row");
+        nbm = xr_div_up((uint64_t)M * V * C, GR_BLOCK);
+        if (nbm > GR_MAX_BMAX) nbm = GR_MAX_BMAX;
+        hipLaunchKernelGGL(k_gr_absmax, dim3(nbm), dim3(GR_BLOCK), 0, st, a, bmax);
+    }
+    hipLaunchKernelGGL(k_gr_scale, dim3(1), dim3(GR_BLOCK), 0, st, (const float*)bmax, nbm, M, scale);
+    if (M != 0) hipLaunchKernelGGL(k_gr_gather_bwd, dim3(xr_div_up((uint64_t)M * V * (C / 4), GR_BLOCK)), dim3(GR_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_gr_gather_cvt, dim3(xr_div_up(el, GR_BLOCK)), dim3(GR_BLOCK), 0, st, (const double*)scale, (const unsigned long long*)acc, el, d_feats);
+    XR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ blend compositor
+struct GrComp {
+    const float* net; uint32_t ld;                     // [M, ld]: rgb (3), density (1), attention (V + 1)
+    const float* source_rgb;                           // [M, V, 3]
+    const int32_t* idx; const int32_t* table;          // flat index per survivor; (count, base) per ray
+    const float* t_vals; const float* noise;           // [R, S]; noise may be null (inference)
+    uint32_t R, S, V, M;
+    int have_z; float z_near, z_far; int white;
+};
+
+// one survivor: colours [own rgb | attention blend], alpha, and (backward) the pieces the chain rule needs
+struct GrSample { float c[3]; float col[6]; float alpha; float raw; float z; uint32_t s; };
+
+static __device__ inline void gr_sample(const GrComp& a, uint32_t r, uint64_t m, GrSample* o) {
+    const float* n = a.net + m * a.ld;
+    uint32_t s = (uint32_t)a.idx[m] - r * a.S;
+    if (s >= a.S) s = a.S - 1;                                     // (an index of another ray: never taken with the hull's table)
+    o->s = s;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o->c[k] = 1.f / (1.f + expf(-n[k]));
+    o->raw = n[3] + (a.noise ? a.noise[(uint64_t)r * a.S + s] : 0.f);
+    o->alpha = 1.f - expf(-(o->raw > 0.f ? o->raw : 0.f));
+    const float* att = n + 4;
+    const float* src = a.source_rgb + m * a.V * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o->col[k] = o->c[k];
+        float b = o->c[k] * att[0];
+        for (uint32_t v = 0; v < a.V; ++v) b += src[3 * v + k] * att[1 + v];
+        o->col[3 + k] = b;
+    }
+    const float t = a.t_vals[(uint64_t)r * a.S + s];
+    o->z = a.have_z ? t * a.z_near + (1.f - t) * a.z_far : 2.f * t - 1.f;
+}
+
+// the ray of this wave and its survivors [base, base + n)
+static __device__ inline bool gr_ray(const GrComp& a, uint32_t* r, uint32_t* n, uint64_t* base) {
+    *r = blockIdx.x * GR_WAVES + (threadIdx.x >> 6);
+    if (*r >= a.R) return false;                                   // (the whole wave)
+    *n = (uint32_t)a.table[2ull * *r];
+    *base = (uint64_t)(uint32_t)a.table[2ull * *r + 1];
+    if (*n > a.S) *n = a.S;
+    if (*base + *n > a.M) *n = *base < a.M ? (uint32_t)(a.M - *base) : 0u;
+    return true;
+}
+
+// wave = ray, lane = survivor, 64 at a time in sample order.  The transmittance in front of a lane is the carry of the chunks before
+// times an exclusive product scan over the lanes (a fixed tree: the same bits every run; the factors of a ray are associated
+// otherwise than by a serial cumprod, which the bars allow for).  weights was cleared by the entry point.
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_comp_fwd(GrComp a, float* __restrict__ rgb_map, float* __restrict__ depth,
+                                                         float* __restrict__ acc, float* __restrict__ weights, float* __restrict__ trans) {
+    uint32_t r, n; uint64_t base;
+    if (!gr_ray(a, &r, &n, &base)) return;
+    const uint32_t lane = threadIdx.x & 63;
+    float carry = 1.f, sum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // 6 colours, depth, acc: per lane, folded at the end
+    for (uint32_t c0 = 0; c0 < n; c0 += 64) {
+        const uint32_t i = c0 + lane;
+        const bool on = i < n;
+        GrSample q;
+        float f = 1.f;
+        if (on) { gr_sample(a, r, base + i, &q); f = (1.f - q.alpha) + 1e-10f; }
+        float incl = f;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float v = __shfl_up(incl, o, 64);
+            if ((int)lane >= o) incl *= v;
+        }
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.f;
+        const float T = carry * excl;
+        if (on) {
+            const float w = q.alpha * T;
+            trans[base + i] = T;
+            weights[(uint64_t)r * a.S + q.s] = w;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) sum[k] += w * q.col[k];
+            sum[6] += w * q.z;
+            sum[7] += w;
+        }
+        carry = carry * __shfl(incl, 63, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum[k] += __shfl_xor(sum[k], off, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) rgb_map[6ull * r + k] = a.white ? sum[k] + (1.f - sum[7]) : sum[k];
+        depth[r] = sum[6];
+        acc[r] = sum[7];
+    }
+}
+
+// the chunks from the last to the first; inside a chunk an inclusive suffix scan of the maps x -> g + f x (g = G alpha), so that
+// C_i = g_i + f_i C_(i+1) and B_i = C_(i+1): d alpha_i = T_i (G_i - B_i), no division by a transmittance, no atomics
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_comp_bwd(GrComp a, const float* __restrict__ d_rgb, const float* __restrict__ trans,
+                                                         float* __restrict__ d_net) {
+    uint32_t r, n; uint64_t base;
+    if (!gr_ray(a, &r, &n, &base)) return;
+    if (n == 0) return;
+    const uint32_t lane = threadIdx.x & 63;
+    float g[6], g_all = 0.f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { g[k] = d_rgb[6ull * r + k]; g_all += g[k]; }
+    const uint32_t cols = 4 + a.V + 1;
+    float carry = 0.f;
+    for (uint32_t c0 = ((n - 1) / 64) * 64 + 64; c0 >= 64; c0 -= 64) {
+        const uint32_t i = c0 - 64 + lane;
+        const bool on = i < n;
+        const uint64_t m = base + i;
+        GrSample q;
+        float G = 0.f, F = 1.f, Cv = 0.f, T = 0.f;
+        if (on) {
+            gr_sample(a, r, m, &q);
+            T = trans[m];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) G += g[k] * q.col[k];
+            if (a.white) G -= g_all;
+            F = (1.f - q.alpha) + 1e-10f;
+            Cv = G * q.alpha;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float F2 = __shfl_down(F, o, 64), C2 = __shfl_down(Cv, o, 64);
+            if ((int)lane + o < 64) { Cv = Cv + F * C2; F = F * F2; }
+        }
+        const float full = Cv + F * carry;
+        float B = __shfl_down(full, 1, 64);
+        if (lane == 63) B = carry;
+        carry = __shfl(full, 0, 64);
+        if (on) {
+            const float w = q.alpha * T;
+            float* o = d_net + m * cols;
+            const float* att = a.net + m * a.ld + 4;
+            const float* src = a.source_rgb + m * a.V * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = (w * (g[k] + att[0] * g[3 + k])) * (q.c[k] * (1.f - q.c[k]));
+            const float d_alpha = T * (G - B);
+            o[3] = q.raw > 0.f ? d_alpha * (1.f - q.alpha) : 0.f;
+            o[4] = w * ((g[3] * q.c[0] + g[4] * q.c[1]) + g[5] * q.c[2]);
+            for (uint32_t v = 0; v < a.V; ++v) o[5 + v] = w * ((g[3] * src[3 * v] + g[4] * src[3 * v + 1]) + g[5] * src[3 * v + 2]);
+        }
+    }
+}
+
+static int gr_comp_args(GrComp* a, const char* fn, const float* net, uint32_t ld, const float* source_rgb, const int32_t* idx,
+                        const int32_t* table, const float* t_vals, const float* noise, uint32_t R, uint32_t S, uint32_t V, uint32_t M,
+                        int have_z, float z_near, float z_far, int white) {
+    if (!table || !t_vals || (M > 0 && (!net || !source_rgb || !idx))) { xr_set_error("%s: null pointer", fn); return XR_EINVAL; }
+    if (V < 1 || V > GR_V) { xr_set_error("%s: 1 .. XR_GNR_MAX_VIEWS source views", fn); return XR_EINVAL; }
+    if (ld < 4 + V + 1) { xr_set_error("%s: the row stride is smaller than rgb, density and attention", fn); return XR_EINVAL; }
+    if (S < 1 || (uint64_t)R * S > (1ull << 30) || (uint64_t)M > (uint64_t)R * S) { xr_set_error("%s: bad ray, sample or survivor count", fn); return XR_EINVAL; }
+    a->net = net; a->ld = ld; a->source_rgb = source_rgb; a->idx = idx; a->table = table; a->t_vals = t_vals; a->noise = noise;
+    a->R = R; a->S = S; a->V = V; a->M = M; a->have_z = have_z ? 1 : 0; a->z_near = z_near; a->z_far = z_far; a->white = white ? 1 : 0;
+    return 0;
+}
+
+extern "C" int xr_gnr_composite_forward(const float* net, uint32_t ld, const float* source_rgb, const int32_t* idx, const int32_t* table,
+                                        const float* t_vals, const float* noise, uint32_t R, uint32_t S, uint32_t V, uint32_t M, int have_z,
+                                        float z_near, float z_far, int white, float* rgb_map, float* depth, float* acc, float* weights,
+                                        float* trans, void* stream) {
+    if (R == 0) return 0;
+    GrComp a;
+    const int rc = gr_comp_args(&a, __func__, net, ld, source_rgb, idx, table, t_vals, noise, R, S, V, M, have_z, z_near, z_far, white);
+    if (rc != 0) return rc;
+    XR_REQUIRE(rgb_map && depth && acc && weights && (M == 0 || trans), "null pointer");
+    XR_HIP(hipMemsetAsync(weights, 0, (size_t)R * S * sizeof(float), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_gr_comp_fwd, dim3(xr_div_up(R, GR_WAVES)), dim3(GR_BLOCK), 0, (hipStream_t)stream, a, rgb_map, depth, acc, weights, trans);
+    XR_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int xr_gnr_composite_backward(const float* net, uint32_t ld, const float* source_rgb, const int32_t* idx, const int32_t* table,
+                                         const float* t_vals, const float* noise, uint32_t R, uint32_t S, uint32_t V, uint32_t M, int white,
+                                         const float* d_rgb_map, const float* trans, float* d_net, void* stream) {
+    if (R == 0 || M == 0) return 0;
+    GrComp a;
+    const int rc = gr_comp_args(&a, __func__, net, ld, source_rgb, idx, table, t_vals, noise, R, S, V, M, 0, 0.f, 0.f, white);
+    if (rc != 0) return rc;
+    XR_REQUIRE(d_rgb_map && trans && d_net, "null pointer");
+    hipLaunchKernelGGL(k_gr_comp_bwd, dim3(xr_div_up(R, GR_WAVES)), dim3(GR_BLOCK), 0, (hipStream_t)stream, a, d_rgb_map, trans, d_net);
+    XR_LAUNCH_CHECK();
+    return 0;
+}

@@ -2110,3 +2110,136 @@ def gnr_shape_embed(pts, near_faces, near_pts, signs, faces, t_verts, center3, r
             _ptr(c3), _ptr(r9), float(scale), float(half),
             int(bool(use_nml)), int(bool(use_t_pose)), int(bool(use_smpl_sdf)), _ptr(out), cols, _ptr(alpha), _stream()), 'xr_gnr_shape_embed')
     return out, alpha
+
+
+# ---------------------------------------------------------------- GNR renderer stages (csrc/xr_gnr_render.hip)
+GNR_MAX_VIEWS = 8               # XR_GNR_MAX_VIEWS
+
+
+def gnr_render_kernels_available():
+    """the loaded library handle has xr_gnr_render.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_gnr_hull_count')
+
+
+def gnr_hull(rays, t_vals, w2c, cams, masks, width, height, depth=None, cam_c=None, rot=None):
+    """visual hull and compaction -> dict: M, table [R,2] int32 (count, base), idx [M] int32, pts [M,3], xy [M,V,2], z [M,V],
+    vis [M,V] bool or None (with depth), attdirs [M,V+1,3] or None (with cam_c).  ONE blocking read (M).  masks / depth [V,H,W]."""
+    rays, t_vals = _f32c(rays).reshape(-1, 6), _f32c(t_vals)
+    R, dev = rays.shape[0], rays.device
+    S = t_vals.shape[-1]
+    w2c, cams = _f32c(w2c).reshape(-1, 4, 4), _f32c(cams)
+    V, cam_cols = w2c.shape[0], cams.shape[-1]
+    masks = _f32c(masks).reshape(V, masks.shape[-2], masks.shape[-1])
+    H, W = masks.shape[-2:]
+    if depth is not None:
+        depth = _f32c(depth).reshape(V, H, W)
+    lib = _lib.load()
+    table = torch.empty((R, 2), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int32, device=dev)
+    rank = _ws(dev, max(R * S, 1) * 4, 'gnr_hull_rank')
+    head = (_ptr(rays), _ptr(t_vals), R, S, _ptr(w2c), _ptr(cams), cam_cols, V, _ptr(masks))
+    with _span('xr_gnr_hull_count', R * S):
+        _lib.check(lib.xr_gnr_hull_count(*head, H, W, float(width), float(height), C.c_void_p(rank.data_ptr()), _ptr(table), _ptr(total),
+                                         _stream()), 'xr_gnr_hull_count')
+    M = int(total.item())
+    out = {'M': M, 'table': table,
+           'idx': torch.empty((M,), dtype=torch.int32, device=dev), 'pts': torch.empty((M, 3), dtype=torch.float32, device=dev),
+           'xy': torch.empty((M, V, 2), dtype=torch.float32, device=dev), 'z': torch.empty((M, V), dtype=torch.float32, device=dev),
+           'vis': None, 'attdirs': None}
+    vis = torch.empty((M, V), dtype=torch.uint8, device=dev) if depth is not None else None
+    if cam_c is not None:
+        cam_c = _f32c(cam_c).reshape(V, 3)
+        out['attdirs'] = torch.empty((M, V + 1, 3), dtype=torch.float32, device=dev)
+    r9 = _f32c(rot).reshape(9) if rot is not None else None
+    if M > 0:
+        with _span('xr_gnr_hull_write', R * S):
+            _lib.check(lib.xr_gnr_hull_write(*head, _ptr(depth), H, W, float(width), float(height), _ptr(cam_c), _ptr(r9),
+                                             C.c_void_p(rank.data_ptr()), _ptr(table), M, _ptr(out['pts']), _ptr(out['idx']), _ptr(out['xy']),
+                                             _ptr(out['z']), _ptr(vis), _ptr(out['attdirs']), _stream()), 'xr_gnr_hull_write')
+    if vis is not None:
+        out['vis'] = vis.bool()
+    return out
+
+
+def gnr_gather(xy, feats_last, images, out=None, col0=0, images_channel_last=False):
+    """pixel-aligned gather: xy [M,V,2], feats_last [V,h,w,C] (channel-last), images [V,3,H,W] (or [V,H,W,3]) ->
+    (out [M,V,ld], source_rgb [M,V,3]); `out` (its last stride is the row stride ld) receives columns col0 .. col0 + C + 3 and zeros
+    behind them; without `out` a fresh [M, V, C + 3 rounded up to 4] buffer is made"""
+    xy = _f32c(xy)
+    M, V = xy.shape[0], xy.shape[1]
+    feats_last, images = _f32c(feats_last), _f32c(images)
+    fh, fw, Cf = feats_last.shape[1:]
+    ih, iw = (images.shape[1], images.shape[2]) if images_channel_last else (images.shape[2], images.shape[3])
+    if out is None:
+        out = torch.empty((M, V, (col0 + Cf + 3 + 3) // 4 * 4), dtype=torch.float32, device=xy.device)
+    if not out.is_contiguous() or out.dtype != torch.float32 or out.shape[:2] != (M, V):
+        raise ValueError('out must be a contiguous float32 [M, V, ld]')
+    source_rgb = torch.empty((M, V, 3), dtype=torch.float32, device=xy.device)
+    with _span('xr_gnr_gather', M * V):
+        _lib.check(_lib.load().xr_gnr_gather(_ptr(xy), M, V, _ptr(feats_last), fh, fw, Cf, _ptr(images), ih, iw, int(bool(images_channel_last)),
+                                             _ptr(out), out.shape[2], int(col0), _ptr(source_rgb), _stream()), 'xr_gnr_gather')
+    return out, source_rgb
+
+
+def gnr_gather_backward(xy, grad, col0, feats_shape):
+    """the gather's gradient in the channel-last feature maps: xy [M,V,2], grad [M,V,ld] (columns col0 .. col0 + C are read),
+    feats_shape = (V, h, w, C) -> d_feats [V,h,w,C]"""
+    xy, grad = _f32c(xy), _f32c(grad)
+    M, V = xy.shape[0], xy.shape[1]
+    Vf, fh, fw, Cf = feats_shape
+    if Vf != V or grad.shape[:2] != (M, V):
+        raise ValueError('shapes of xy %r, grad %r and the feature maps %r disagree' % (tuple(xy.shape), tuple(grad.shape), tuple(feats_shape)))
+    lib = _lib.load()
+    d_feats = torch.empty((V, fh, fw, Cf), dtype=torch.float32, device=xy.device)
+    nbytes = int(lib.xr_gnr_gather_backward_workspace_bytes(V, fh, fw, Cf))
+    ws = _ws(xy.device, nbytes, 'gnr_gather_bwd')
+    with _span('xr_gnr_gather_backward', M * V):
+        _lib.check(lib.xr_gnr_gather_backward(_ptr(xy), M, V, _ptr(grad), grad.shape[2], int(col0), fh, fw, Cf, _ptr(d_feats),
+                                              C.c_void_p(ws.data_ptr()), ws.numel(), _stream()), 'xr_gnr_gather_backward')
+    return d_feats
+
+
+def _gnr_comp_head(net, source_rgb, idx, table, t_vals, noise):
+    if net.dim() != 2 or net.stride(1) != 1 or net.dtype != torch.float32:
+        raise ValueError('net must be float32 [M, ld] with unit column stride')
+    if net.shape[0] > 1 and net.stride(0) < net.shape[1]:
+        raise ValueError('net rows overlap')
+    source_rgb, idx, table, t_vals = _f32c(source_rgb), _i32c(idx), _i32c(table), _f32c(t_vals)
+    noise = _f32c(noise) if noise is not None else None
+    R, S = t_vals.shape
+    M, V = net.shape[0], source_rgb.shape[1] if source_rgb.dim() == 3 else 0
+    if net.shape[1] < 4 + V + 1 or idx.shape[0] != M or source_rgb.shape[0] != M or table.shape != (R, 2):
+        raise ValueError('shapes of net %r, source_rgb %r, idx %r, table %r disagree' % (tuple(net.shape), tuple(source_rgb.shape),
+                                                                                         tuple(idx.shape), tuple(table.shape)))
+    ld = net.stride(0) if M > 1 else max(net.shape[1], 4 + V + 1)
+    keep = (net, source_rgb, idx, table, t_vals, noise)
+    return (C.c_void_p(net.data_ptr()) if M else None, ld, _ptr(source_rgb) if M else None, _ptr(idx) if M else None, _ptr(table),
+            _ptr(t_vals), _ptr(noise), R, S, V, M), keep
+
+
+def gnr_composite_forward(net, source_rgb, idx, table, t_vals, noise=None, z_near_far=None, white=False):
+    """-> (rgb_map [R,6], depth [R], acc [R], weights [R,S], trans [M])"""
+    head, keep = _gnr_comp_head(net, source_rgb, idx, table, t_vals, noise)
+    R, S, M = head[7], head[8], head[10]
+    dev = keep[4].device
+    rgb_map = torch.empty((R, 6), dtype=torch.float32, device=dev)
+    depth, acc = torch.empty((R,), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.float32, device=dev)
+    weights = torch.empty((R, S), dtype=torch.float32, device=dev)
+    trans = torch.empty((M,), dtype=torch.float32, device=dev)
+    zn, zf = (float(z_near_far[0]), float(z_near_far[1])) if z_near_far is not None else (0.0, 0.0)
+    with _span('xr_gnr_composite_forward', R):
+        _lib.check(_lib.load().xr_gnr_composite_forward(*head, int(z_near_far is not None), zn, zf, int(bool(white)), _ptr(rgb_map), _ptr(depth),
+                                                        _ptr(acc), _ptr(weights), _ptr(trans), _stream()), 'xr_gnr_composite_forward')
+    return rgb_map, depth, acc, weights, trans
+
+
+def gnr_composite_backward(net, source_rgb, idx, table, t_vals, noise, white, d_rgb_map, trans):
+    """-> d_net [M, 4 + V + 1]"""
+    head, keep = _gnr_comp_head(net, source_rgb, idx, table, t_vals, noise)
+    R, V, M = head[7], head[9], head[10]
+    d_rgb_map, trans = _f32c(d_rgb_map).reshape(R, 6), _f32c(trans)
+    d_net = torch.empty((M, 4 + V + 1), dtype=torch.float32, device=keep[4].device)
+    with _span('xr_gnr_composite_backward', R):
+        _lib.check(_lib.load().xr_gnr_composite_backward(*head, int(bool(white)), _ptr(d_rgb_map), _ptr(trans), _ptr(d_net), _stream()),
+                                                         'xr_gnr_composite_backward')
+    return d_net
