@@ -60,18 +60,15 @@ def test_fixture_network_train_step_and_stage_loop(edev, gold):
 
 
 @pytest.mark.parametrize('R,S', [(5, 7), (3, 64), (9, 100), (1, 1), (66, 16)])
-def test_kernels_against_restatement(E, R, S):
+def test_kernels_against_restatement(E, edev, R, S):
     import bungee_restatement as RS
+    import test_gpu_bungee as T
     L = E.lib('xr_bungee')
     for name, (res, args) in __import__('xrnerf_amd._lib', fromlist=['x']).BUNGEE_SIGNATURES.items():
         getattr(L, name).restype, getattr(L, name).argtypes = res, args
-    rng = np.random.default_rng(R * 1000 + S)
-    s = 1 / 400
-    o = E.f32(np.stack([rng.uniform(-1, 1, R), rng.uniform(-1, 1, R), rng.uniform(1.5, 8, R)], -1))
-    d = rng.normal(0, 0.2, (R, 3)) - [0, 0, 1]
-    d = E.f32(d / np.linalg.norm(d, axis=-1, keepdims=True))
-    vd = d.copy()
-    radii = E.f32(rng.uniform(1e-4, 1e-3, (R, 1)))
+    sc = T.restatement_rays(R, S)
+    s = T.SCALE
+    o, d, vd, radii = sc['o'], sc['d'], sc['vd'], sc['radii']
     near, far = np.zeros(R, np.float32), np.zeros(R, np.float32)
     z = np.zeros((R, S + 1), np.float32)
     gc = (C.c_float * 3)(0., 0., -6371011.0 * s)
@@ -89,24 +86,4 @@ def test_kernels_against_restatement(E, R, S):
     means, covs = RS.gaussians(t(z), t(o), t(d), t(radii))
     e64 = RS.embed(means, covs, t(vd)).numpy()
     assert np.abs(out[:, :cp + cd] - e64).max() <= 1e-3            # arguments up to 512 |x| ~ 4e3: fp32 rounding of the mean
-    Hh = 3
-    raw = E.aligned((R, S, Hh, 4), fill=rng.normal(0, 1.5, (R, S, Hh, 4)))
-    noise = E.f32(rng.normal(0, 1, (R, S)))
-    g = E.f32(rng.normal(0, 1, (R, 3)))
-    for stage, nz in ((0, None), (1, noise), (2, None), (5, None)):
-        rgb, disp, acc, w = np.zeros((R, 3), np.float32), np.zeros(R, np.float32), np.zeros(R, np.float32), np.zeros((R, S), np.float32)
-        E.check(L.xr_bungee_render_forward(E.p(raw), E.p(z), E.p(vd), E.p(nz), R, S + 1, Hh, stage, -1.0, 0.0, 0, 0, E.p(rgb), E.p(disp),
-                                           E.p(acc), E.p(w), None), L)
-        r64 = t(raw).requires_grad_(True)
-        orgb, odisp, oacc, ow = RS.render(r64, t(z), t(vd), stage, None if nz is None else t(nz))
-        (orgb * t(g)).sum().backward()
-        assert np.abs(w - ow.detach().numpy()).max() <= 2e-6
-        assert np.abs(rgb - orgb.detach().numpy()).max() <= 1e-5 and np.abs(acc - oacc.detach().numpy()).max() <= 1e-5
-        od = odisp.detach().numpy()
-        assert np.abs(disp - od).max() <= 1e-5 * np.abs(od).max()
-        graw = E.aligned((R, S, Hh, 4), fill=np.nan)
-        E.check(L.xr_bungee_render_backward(E.p(raw), E.p(z), E.p(vd), E.p(nz), E.p(g), R, S + 1, Hh, stage, -1.0, 0.0, 0, 0,
-                                            E.p(graw), None), L)
-        og = r64.grad.numpy()
-        assert np.abs(graw - og).max() <= 1e-5 * max(1.0, np.abs(og).max())
-        assert (graw[:, :, stage + 1:] == 0).all()
+    T.check_render_restatement(edev, R, S)          # the renderer: the body of the GPU test, through the emulated ops

@@ -109,6 +109,58 @@ def check_render(dev, gold):
     assert np.abs(g - gold['rn_graw']).max() <= 1e-5 * np.abs(gold['rn_graw']).max()
 
 
+_RAYS = {}
+GLOBE = (0., 0., -6371011.0)
+SCALE = 1 / 400
+
+
+def restatement_rays(R, S):
+    """seeded cameras above the globe looking down, raw [R, S, 3 heads, 4], density noise and dL/drgb as float32 numpy; drawn once per
+    shape and shared (tests/test_emu_bungee.py runs its kernels on the same rays)"""
+    if (R, S) not in _RAYS:
+        rng = np.random.default_rng(R * 1000 + S)
+        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        o = f32(np.stack([rng.uniform(-1, 1, R), rng.uniform(-1, 1, R), rng.uniform(1.5, 8, R)], -1))
+        d = rng.normal(0, 0.2, (R, 3)) - [0, 0, 1]
+        d = f32(d / np.linalg.norm(d, axis=-1, keepdims=True))
+        radii = f32(rng.uniform(1e-4, 1e-3, (R, 1)))
+        raw = f32(rng.normal(0, 1.5, (R, S, 3, 4)))
+        noise = f32(rng.normal(0, 1, (R, S)))
+        g = f32(rng.normal(0, 1, (R, 3)))
+        _RAYS[(R, S)] = dict(o=o, d=d, vd=d.copy(), radii=radii, raw=raw, noise=noise, g=g)
+    return _RAYS[(R, S)]
+
+
+def check_render_restatement(dev, R, S):
+    """renderer forward / backward of R rays x S intervals against the float64 restatement: stages 0, 1 with noise, 2 and 5 of 3 heads
+    (softplus, density_bias -1, no padding, black background).  S = 64 is exactly one sweep of the wave, S = 100 two with a ragged last."""
+    import bungee_restatement as RS
+    from xrnerf_amd import ops
+    sc = restatement_rays(R, S)
+    t64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+    vd, raw, g = _t(sc['vd'], dev), _t(sc['raw'], dev), _t(sc['g'], dev)
+    _, _, z = ops.bungee_zvals(_t(sc['o'], dev), vd, None, None, S + 1, 'sphere', GLOBE, SCALE)
+    z64 = t64(z.cpu().numpy())
+    for stage, nz in ((0, None), (1, sc['noise']), (2, None), (5, None)):
+        noise = None if nz is None else _t(nz, dev)
+        rgb, disp, acc, w = [v.cpu().numpy() for v in ops.bungee_render_forward(raw, z, vd, stage, noise=noise)]
+        r64 = t64(sc['raw']).requires_grad_(True)
+        orgb, odisp, oacc, ow = RS.render(r64, z64, t64(sc['vd']), stage, None if nz is None else t64(nz))
+        (orgb * t64(sc['g'])).sum().backward()
+        od, og = odisp.detach().numpy(), r64.grad.numpy()
+        e_w, e_rgb = np.abs(w - ow.detach().numpy()).max(), np.abs(rgb - orgb.detach().numpy()).max()
+        e_acc, e_disp = np.abs(acc - oacc.detach().numpy()).max(), np.abs(disp - od).max()
+        graw = ops.bungee_render_backward(raw, z, vd, g, stage, noise=noise).cpu().numpy()
+        e_g = np.abs(graw - og).max()
+        print('bungee render R=%d S=%d stage=%d: w %.3g rgb %.3g acc %.3g disp %.3g of max %.3g  grad %.3g of max %.3g' % (
+            R, S, stage, e_w, e_rgb, e_acc, e_disp, np.abs(od).max(), e_g, np.abs(og).max()))
+        assert e_w <= 2e-6
+        assert e_rgb <= 1e-5 and e_acc <= 1e-5
+        assert e_disp <= 1e-5 * np.abs(od).max()
+        assert e_g <= 1e-5 * max(1.0, np.abs(og).max())
+        assert (graw[:, :, stage + 1:] == 0).all()
+
+
 def check_resample(dev, gold):
     from xrnerf_amd import mip
     b = batch(gold, dev)
@@ -189,6 +241,12 @@ def test_encode_against_reference(dev, gold):
 
 def test_render_against_reference(dev, gold):
     check_render(dev, gold)
+
+
+@pytest.mark.parametrize('R,S', [(5, 7), (3, 64), (9, 100)])
+def test_render_against_restatement_across_sweeps(dev, R, S):
+    """a partial block of waves, exactly one 64-interval sweep, two sweeps with a ragged last one"""
+    check_render_restatement(dev, R, S)
 
 
 def test_resample_against_reference(dev, gold):

@@ -22,6 +22,7 @@ from . import builder, mlp_graph as G, ops
 from .builder import EMBEDDERS, MLPS, NETWORKS, RENDERS
 from .mip import MipSamples, resample_along_rays, sample_along_rays
 from .networks import BaseNerfNetwork, get_dist_info, img2mse, mse2psnr, recover_shape, unfold_batching
+from .renders import RayRender
 from .vanilla import merge_ret
 
 
@@ -341,25 +342,6 @@ class _BungeeMlpFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------ renderer
-class _BungeeRenderFn(torch.autograd.Function):
-    """renderer forward / backward as one launch each; gradients flow from the colours only (weights feed the detached resampler)"""
-
-    @staticmethod
-    def forward(ctx, raw, z_vals, viewdirs, noise, stage, density_bias, rgb_padding, white_bkgd, act):
-        rgb, disp, acc, w = ops.bungee_render_forward(raw, z_vals, viewdirs, stage, density_bias, rgb_padding, white_bkgd, act, noise)
-        ctx.save_for_backward(raw, z_vals, viewdirs)
-        ctx.noise = noise
-        ctx.cfg = (stage, density_bias, rgb_padding, white_bkgd, act)
-        ctx.mark_non_differentiable(disp, acc, w)
-        return rgb, disp, acc, w
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_disp, g_acc, g_w):
-        raw, z_vals, viewdirs = ctx.saved_tensors
-        g = ops.bungee_render_backward(raw, z_vals, viewdirs, g_rgb.contiguous(), *ctx.cfg, noise=ctx.noise)
-        return (g,) + (None,) * 8
-
-
 @RENDERS.register_module()
 class BungeeNerfRender(nn.Module):
     """renders/bungeenerf_render.py: heads 0..stage summed, midpoint distances times |viewdirs|, cumprod weights"""
@@ -379,9 +361,9 @@ class BungeeNerfRender(nn.Module):
         noise_std = 0 if is_test else self.raw_noise_std
         if noise is None and noise_std > 0.:
             noise = (torch.randn(raw.shape[:2]) * noise_std).to(raw.device)          # drawn on the host, as the reference does
-        rgb, disp, acc, w = _BungeeRenderFn.apply(raw, z_vals, data['viewdirs'], noise if noise_std > 0. else None, int(self.stage),
-                                                  float(self.density_bias), float(self.rgb_padding), bool(self.white_bkgd),
-                                                  self.density_activation)
+        rgb, disp, acc, w = RayRender.apply(ops.bungee_render_forward, ops.bungee_render_backward, raw, z_vals, data['viewdirs'],
+                                            noise if noise_std > 0. else None, int(self.stage), float(self.density_bias),
+                                            float(self.rgb_padding), bool(self.white_bkgd), self.density_activation)
         data['weights'] = w
         return data, {'rgb': rgb, 'disp': disp, 'acc': acc}
 

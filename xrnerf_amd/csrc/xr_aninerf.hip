@@ -15,6 +15,7 @@
 // Compiled with -ffp-contract=off: every expression is fp32 in the written order (the fp32 torch restatement of the query matches it
 // bit for bit).
 #include "xr_common.h"
+#include "xr_wave.h"
 #include "../../include/xrnerf_mi355_aninerf.h"
 
 #define AN_BLOCK 256
@@ -150,12 +151,7 @@ __global__ void __launch_bounds__(AN_BLOCK) k_ani_select_order(const int32_t* __
     for (uint32_t b0 = 0; b0 < nb; b0 += AN_BLOCK) {
         const uint32_t b = b0 + t;
         const uint32_t c = b < nb ? ws.cnt[b] + (b == extra_block ? 1u : 0u) : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if ((int)lane >= off) incl += o;
-        }
+        const uint32_t incl = xr_wave_incl_sum(c);
         __syncthreads();                                           // s_w of the previous sweep has been read
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();

@@ -5,8 +5,9 @@
 //   k_bungee_zvals     thread = ray: sphere / flat bounds, disparity-then-depth edges, the reference's sort
 //   k_bungee_encode    workgroup = 64 consecutive samples; gaussians in LDS, the per-ray direction features once per ray of the tile,
 //                      then the lanes sweep (sample, frequency, axis) items, one exp factor shared by the sin and the cos column
-//   k_bungee_render_*  wave = ray; 64 intervals per sweep, transmittance as an fp64 prefix PRODUCT of (1 - alpha + 1e-10)
-//                      (torch's CPU cumprod accumulates fp32 in double), fixed-order butterflies for the sums
+//   k_bungee_render_*  wave = ray; 64 intervals per sweep: the forward sweep and the backward's pass body of xr_render.h with the policy
+//                      BungeeRender; transmittance as an fp64 prefix PRODUCT of (1 - alpha + 1e-10) (torch's CPU cumprod
+//                      accumulates fp32 in double), fixed-order butterflies for the sums
 // Compiled with -ffp-contract=off: every expression is fp32 in the reference's operation order.
 //
 // Bounds precision.  The sphere mode intersects spheres of earth radius (6371011 m times the scene scaling): |o - c|^2 - r^2 subtracts
@@ -17,7 +18,7 @@
 // expressions the same way, not to the precision fp64 would give.
 #include "xr_common.h"
 #include "xr_mip_math.h"
-#include "xr_wave.h"
+#include "xr_render.h"
 
 #define BG_TILE 64
 #define BG_BLOCK 256
@@ -197,43 +198,27 @@ static __device__ inline BungeeSample bg_load(const BungeeRenderArgs& a, uint32_
 }
 static __device__ inline float bg_rgb(const BungeeRenderArgs& a, float x) { return a.rgb_k / (1.f + expf(-x)) - a.rgb_padding; }
 
+// the policy of xr_render.h: the forward sweep, and the pass body of the two-pass backward
+struct BungeeRender {
+    typedef BungeeSample Sample;
+    typedef XrCumprodStep Step;
+    BungeeRenderArgs a;
+    float vnorm;
+    __device__ void ray(uint32_t r) { vnorm = bg_norm3(a.viewdirs[r * 3ull], a.viewdirs[r * 3ull + 1], a.viewdirs[r * 3ull + 2]); }
+    __device__ BungeeSample load(uint32_t r, uint32_t i) const { return bg_load(a, r, i, vnorm); }
+    __device__ double step_in(const BungeeSample& s) const { return (double)s.f; }
+    __device__ float weight(const BungeeSample& s, float T) const { return (1.f - expf(s.dd)) * T; }
+    __device__ void colours(const BungeeSample& s, float* c) const {
+        for (int k = 0; k < 3; ++k) c[k] = bg_rgb(a, s.a_rgb[k]);
+    }
+    __device__ float depth(const BungeeSample& s) const { return s.zmid; }
+    __device__ float ray_scalar(uint32_t, float depth, float acc) const { return xr_render_disp(depth, acc); }
+};
+
 __global__ void __launch_bounds__(BG_BLOCK) k_bungee_render_fwd(BungeeRenderArgs a, float* __restrict__ rgb_out,
                                                                 float* __restrict__ disp_out, float* __restrict__ acc_out,
                                                                 float* __restrict__ weights_out) {
-    const uint32_t r = blockIdx.x * (BG_BLOCK / 64) + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    if (r >= a.n_rays) return;                 // whole waves leave together
-    const float vnorm = bg_norm3(a.viewdirs[r * 3ull], a.viewdirs[r * 3ull + 1], a.viewdirs[r * 3ull + 2]);
-    double carry = 1.0;                        // prod of (1 - alpha + 1e-10) over the intervals before this sweep
-    float acc_c[3] = {0.f, 0.f, 0.f}, acc_w = 0.f, acc_z = 0.f;
-    for (uint32_t base = 0; base < a.n_s; base += 64) {
-        const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        BungeeSample s;
-        double f = 1.0;
-        if (live) { s = bg_load(a, r, i, vnorm); f = (double)s.f; }
-        const double incl = xr_wave_incl_prod(f);
-        const double excl = xr_wave_excl_of_prod(incl);                       // all lanes take part in the shuffle
-        if (live) {
-            const float T = (float)(carry * excl);                       // exclusive: the prefix before this lane
-            const float alpha = 1.f - expf(s.dd);
-            const float w = alpha * T;
-            weights_out[(uint64_t)r * a.n_s + i] = w;
-            acc_w += w;
-            acc_z += w * s.zmid;
-            for (int c = 0; c < 3; ++c) acc_c[c] += w * bg_rgb(a, s.a_rgb[c]);
-        }
-        carry *= __shfl(incl, 63, 64);
-    }
-    const float acc = xr_wave_sum(acc_w), depth = xr_wave_sum(acc_z);
-    float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(acc_c[c]);
-    if (lane == 0) {
-        const float q = depth / acc;
-        disp_out[r] = 1.f / (q != q ? q : fmaxf(1e-10f, q));          // torch.max propagates NaN
-        acc_out[r] = acc;
-        for (int c = 0; c < 3; ++c) rgb_out[r * 3ull + c] = a.white_bkgd ? col[c] + (1.f - acc) : col[c];
-    }
+    xr_render_fwd(BungeeRender{a, 0.f}, blockIdx.x * (BG_BLOCK / 64) + (threadIdx.x >> 6), rgb_out, disp_out, acc_out, weights_out);
 }
 
 // dL/draw given dL/drgb.  With gc_i = sum_ch g_ch (rgb_i,ch - [white]), w_i = alpha_i T_i, T_i = prod_{j<i} f_j, f_j = 1 - alpha_j + 1e-10:
@@ -245,62 +230,36 @@ __global__ void __launch_bounds__(BG_BLOCK) k_bungee_render_bwd(BungeeRenderArgs
     const uint32_t r = blockIdx.x * (BG_BLOCK / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     if (r >= a.n_rays) return;
-    const float vnorm = bg_norm3(a.viewdirs[r * 3ull], a.viewdirs[r * 3ull + 1], a.viewdirs[r * 3ull + 2]);
+    BungeeRender p{a, 0.f};
+    p.ray(r);
     const float g[3] = {grad_rgb[r * 3ull], grad_rgb[r * 3ull + 1], grad_rgb[r * 3ull + 2]};
     const float white = a.white_bkgd ? 1.f : 0.f;
     // pass 1: total = sum_i w_i gc_i
-    double carry = 1.0, total = 0.0;
-    for (uint32_t base = 0; base < a.n_s; base += 64) {
-        const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        BungeeSample s;
-        double f = 1.0, wg = 0.0;
-        if (live) { s = bg_load(a, r, i, vnorm); f = (double)s.f; }
-        const double incl = xr_wave_incl_prod(f);
-        const double excl = xr_wave_excl_of_prod(incl);
-        if (live) {
-            const float w = (1.f - expf(s.dd)) * (float)(carry * excl);
-            float gc = 0.f;
-            for (int c = 0; c < 3; ++c) gc += g[c] * (bg_rgb(a, s.a_rgb[c]) - white);
-            wg = (double)w * (double)gc;
-        }
-        total += xr_wave_sum(wg);
-        carry *= __shfl(incl, 63, 64);
-    }
+    double total = 0.0;
+    XrCumprodStep st;
+    for (uint32_t base = 0; base < a.n_s; base += 64) total += xr_wave_sum(xr_render_term(p, st, r, base + lane, g, white).wg);
     // pass 2: gradients
-    carry = 1.0;
+    st = XrCumprodStep();
     double carry_wg = 0.0;
     for (uint32_t base = 0; base < a.n_s; base += 64) {
         const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        BungeeSample s;
-        double f = 1.0, wg = 0.0;
-        float w = 0.f, gc = 0.f, T = 0.f;
-        if (live) { s = bg_load(a, r, i, vnorm); f = (double)s.f; }
-        const double incl = xr_wave_incl_prod(f);
-        const double excl = xr_wave_excl_of_prod(incl);
-        if (live) {
-            T = (float)(carry * excl);
-            w = (1.f - expf(s.dd)) * T;
-            for (int c = 0; c < 3; ++c) gc += g[c] * (bg_rgb(a, s.a_rgb[c]) - white);
-            wg = (double)w * (double)gc;
-        }
-        const double incl_wg = xr_wave_incl_sum(wg);
-        if (live) {
+        const XrRenderTerm<BungeeRender> q = xr_render_term(p, st, r, i, g, white);
+        const BungeeSample& s = q.s;
+        const double incl_wg = xr_wave_incl_sum(q.wg);
+        if (i < a.n_s) {
             const double suffix = total - (carry_wg + incl_wg);
-            const float d_alpha = (float)((double)(T * gc) - suffix / f);
+            const float d_alpha = (float)((double)(q.t * q.gc) - suffix / (double)s.f);
             const float ed = expf(s.dd);
             float4 o;
             float* oc = &o.x;
             for (int c = 0; c < 3; ++c) {
                 const float e = expf(-s.a_rgb[c]), den = 1.f + e;
-                oc[c] = g[c] * w * (a.rgb_k * e / (den * den));
+                oc[c] = g[c] * q.w * (a.rgb_k * e / (den * den));
             }
             o.w = d_alpha * ed * xr_mip_density_dact(s.x, a.relu) * s.dist;
-            float4* p = reinterpret_cast<float4*>(grad_raw) + ((uint64_t)r * a.n_s + i) * a.n_heads;
-            for (uint32_t h = 0; h < a.n_heads; ++h) p[h] = h < a.n_used ? o : make_float4(0.f, 0.f, 0.f, 0.f);
+            float4* out = reinterpret_cast<float4*>(grad_raw) + ((uint64_t)r * a.n_s + i) * a.n_heads;
+            for (uint32_t h = 0; h < a.n_heads; ++h) out[h] = h < a.n_used ? o : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        carry *= __shfl(incl, 63, 64);
         carry_wg += __shfl(incl_wg, 63, 64);
     }
 }

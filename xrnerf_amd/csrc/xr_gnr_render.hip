@@ -16,6 +16,7 @@
 //   k_gr_comp_bwd  wave = ray, the chunks backwards with a suffix scan of B <- G alpha + (1 - alpha + 1e-10) B; no division by a
 //                  transmittance, no atomics
 #include "xr_common.h"
+#include "xr_wave.h"
 #include "../../include/xrnerf_mi355_gnr.h"
 
 #define GR_BLOCK 256
@@ -114,12 +115,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_scan(uint32_t R, int32_t* __res
     for (uint32_t b0 = 0; b0 < R; b0 += GR_BLOCK) {
         const uint32_t b = b0 + t;
         const uint32_t c = b < R ? (uint32_t)table[2ull * b] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += v;
-        }
+        const uint32_t incl = xr_wave_incl_sum(c);
         __syncthreads();                                           // s_w of the previous sweep has been read
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
@@ -495,15 +491,8 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_comp_fwd(GrComp a, float* __res
         GrSample q;
         float f = 1.f;
         if (on) { gr_sample(a, r, base + i, &q); f = (1.f - q.alpha) + 1e-10f; }
-        float incl = f;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float v = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl *= v;
-        }
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float T = carry * excl;
+        const float incl = xr_wave_incl_prod(f);
+        const float T = carry * xr_wave_excl_of_prod(incl);
         if (on) {
             const float w = q.alpha * T;
             trans[base + i] = T;
@@ -516,10 +505,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_comp_fwd(GrComp a, float* __res
         carry = carry * __shfl(incl, 63, 64);
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum[k] += __shfl_xor(sum[k], off, 64);
-    }
+    for (int k = 0; k < 8; ++k) sum[k] = xr_wave_sum(sum[k]);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) rgb_map[6ull * r + k] = a.white ? sum[k] + (1.f - sum[7]) : sum[k];
@@ -556,11 +542,8 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_comp_bwd(GrComp a, const float*
             F = (1.f - q.alpha) + 1e-10f;
             Cv = G * q.alpha;
         }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float F2 = __shfl_down(F, o, 64), C2 = __shfl_down(Cv, o, 64);
-            if ((int)lane + o < 64) { Cv = Cv + F * C2; F = F * F2; }
-        }
+        const XrAffine<float> sc = xr_wave_affine_rscan(F, Cv);
+        F = sc.F; Cv = sc.A;
         const float full = Cv + F * carry;
         float B = __shfl_down(full, 1, 64);
         if (lane == 63) B = carry;

@@ -23,7 +23,7 @@
 // Bound: fp32 MFMA (157.3 TFLOP/s; 12.2 kflop per evaluated sample + 3 padded K slots per Fourier group) for
 // k_kilo_mlp, HBM for the rest.
 #include "xr_common.h"
-#include "xr_wave.h"
+#include "xr_render.h"
 #include "xr_adam.h"            // adam1: the students' fused update
 #include "xr_mip_math.h"      // xr_mip_zval: GetZvals' linspace (datasets/pipelines/create.py:502-516)
 
@@ -614,7 +614,7 @@ __global__ void __launch_bounds__(256) k_nerf_render(const float4* __restrict__ 
     if (r >= zr.n_rays) return;
     const float dx = zr.rays_d[r * 3ull], dy = zr.rays_d[r * 3ull + 1], dz = zr.rays_d[r * 3ull + 2];
     const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-    double carry = 1.0;                                  // prod_{j < sweep} (1 - alpha_j + 1e-10)
+    XrCumprodStep st;                                    // carries prod_{j < sweep} (1 - alpha_j + 1e-10)
     float a_c[3] = {0.f, 0.f, 0.f}, a_w = 0.f, a_z = 0.f;
     const uint32_t s_lo = spans != nullptr ? spans[2 * r] : 0u, s_hi = spans != nullptr ? spans[2 * r + 1] : n_s;
     for (uint32_t base = s_lo & ~63u; base < s_hi; base += 64) {
@@ -638,10 +638,9 @@ __global__ void __launch_bounds__(256) k_nerf_render(const float4* __restrict__ 
             if (live && weights_out != nullptr) weights_out[(uint64_t)r * n_s + i] = 0.f;
             continue;
         }
-        const double incl = xr_wave_incl_prod(fac);
-        const double excl = xr_wave_excl_of_prod(incl);      // (a factor can be exactly 0)
+        const float T = st.step(fac);                    // (a factor can be exactly 0: no division)
         if (live) {
-            const float w = alpha * (float)(carry * excl);
+            const float w = alpha * T;
             if (weights_out != nullptr) weights_out[(uint64_t)r * n_s + i] = w;
             a_w += w;
             a_z += w * zi;
@@ -649,7 +648,6 @@ __global__ void __launch_bounds__(256) k_nerf_render(const float4* __restrict__ 
             a_c[1] += w * (1.f / (1.f + expf(-v.y)));
             a_c[2] += w * (1.f / (1.f + expf(-v.z)));
         }
-        carry *= __shfl(incl, 63, 64);
     }
     const float acc = xr_wave_sum(a_w), depth = xr_wave_sum(a_z);
     float col[3];

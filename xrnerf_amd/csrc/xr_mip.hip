@@ -7,13 +7,14 @@
 //   k_mip_encode    workgroup = 64 consecutive samples; the gaussians are built once per sample in LDS, then the
 //                   lanes sweep the tile's flattened [64 x ch] output so that every store is a fully coalesced
 //                   dword row segment (ch = 123 floats = 492 B/sample, not 16-B aligned: no vector stores)
-//   k_mip_render*   wave = ray; 64 intervals per sweep, transmittance through a wave-wide fp64 prefix sum
-//                   (torch's CPU cumsum accumulates fp32 in double), reductions by butterfly
+//   k_mip_render*   wave = ray; 64 intervals per sweep: the forward sweep and the backward's pass body of xr_render.h
+//                   with the policy MipRender; transmittance through a wave-wide fp64 prefix sum (torch's CPU cumsum
+//                   accumulates fp32 in double), reductions by butterfly
 //   k_mip_resample  wave = ray; blurred pdf -> fp64 scan -> cdf in LDS -> per-output binary search
 // All HBM-streaming: bytes per unit are in DESIGN.md section 8.
 #include "xr_common.h"
 #include "xr_mip_math.h"
-#include "xr_wave.h"
+#include "xr_render.h"
 
 #define MIP_TILE 64
 #define MIP_BLOCK 256
@@ -108,45 +109,36 @@ __device__ inline MipSample mip_load_sample(const MipRenderArgs& a, uint32_t r, 
     return s;
 }
 
-__global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_fwd(MipRenderArgs a, float* __restrict__ rgb_out,
-                                                              float* __restrict__ dist_out, float* __restrict__ acc_out,
-                                                              float* __restrict__ weights_out) {
-    const uint32_t r = blockIdx.x * (MIP_BLOCK / 64) + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    if (r >= a.n_rays) return;                 // whole waves leave together
-    const float dx = a.rays_d[r * 3ull], dy = a.rays_d[r * 3ull + 1], dz = a.rays_d[r * 3ull + 2];
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-    double carry = 0.0;                        // sum of density_delta over the intervals before this sweep
-    float acc_c[3] = {0.f, 0.f, 0.f}, acc_w = 0.f, acc_z = 0.f;
-    for (uint32_t base = 0; base < a.n_s; base += 64) {
-        const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        MipSample s;
-        double dd = 0.0;
-        if (live) { s = mip_load_sample(a, r, i, dnorm); dd = (double)s.dd; }
-        const double incl = xr_wave_incl_sum(dd);
-        if (live) {
-            const float before = (float)(carry + (incl - dd));          // exclusive cumsum, rounded like torch's output
-            const float w = (1.f - expf(-s.dd)) * expf(-before);
-            weights_out[(uint64_t)r * a.n_s + i] = w;
-            acc_w += w;
-            acc_z += w * s.zmid;
-            for (int c = 0; c < 3; ++c) acc_c[c] += w * s.rgb[c];
-        }
-        carry += __shfl(incl, 63, 64);
+// the policy of xr_render.h: the forward sweep, and the pass body of the two-pass backward
+struct MipRender {
+    typedef MipSample Sample;
+    typedef XrCumsumStep Step;
+    MipRenderArgs a;
+    float dnorm;
+    __device__ void ray(uint32_t r) {
+        const float dx = a.rays_d[r * 3ull], dy = a.rays_d[r * 3ull + 1], dz = a.rays_d[r * 3ull + 2];
+        dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
     }
-    const float acc = xr_wave_sum(acc_w), depth = xr_wave_sum(acc_z);
-    float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(acc_c[c]);
-    if (lane == 0) {
+    __device__ MipSample load(uint32_t r, uint32_t i) const { return mip_load_sample(a, r, i, dnorm); }
+    __device__ double step_in(const MipSample& s) const { return (double)s.dd; }
+    // `before`: the exclusive cumsum of density_delta, rounded like torch's output
+    __device__ float weight(const MipSample& s, float before) const { return (1.f - expf(-s.dd)) * expf(-before); }
+    __device__ void colours(const MipSample& s, float* c) const {
+        for (int k = 0; k < 3; ++k) c[k] = s.rgb[k];
+    }
+    __device__ float depth(const MipSample& s) const { return s.zmid; }
+    __device__ float ray_scalar(uint32_t r, float depth, float acc) const {
         const float* z = a.z_vals + (uint64_t)r * (a.n_s + 1);
         float q = depth / acc;                                          // mipnerf_render.py:17-23
         if (q != q) q = INFINITY;
-        q = fmaxf(fminf(q, z[a.n_s]), z[0]);
-        dist_out[r] = q;
-        acc_out[r] = acc;
-        for (int c = 0; c < 3; ++c) rgb_out[r * 3ull + c] = a.white_bkgd ? col[c] + (1.f - acc) : col[c];
+        return fmaxf(fminf(q, z[a.n_s]), z[0]);
     }
+};
+
+__global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_fwd(MipRenderArgs a, float* __restrict__ rgb_out,
+                                                              float* __restrict__ dist_out, float* __restrict__ acc_out,
+                                                              float* __restrict__ weights_out) {
+    xr_render_fwd(MipRender{a, 0.f}, blockIdx.x * (MIP_BLOCK / 64) + (threadIdx.x >> 6), rgb_out, dist_out, acc_out, weights_out);
 }
 
 // dL/draw given dL/drgb (the reference trains on the rendered colours only, networks/mipnerf.py:52-60).
@@ -157,60 +149,34 @@ __global__ void __launch_bounds__(MIP_BLOCK) k_mip_render_bwd(MipRenderArgs a, c
     const uint32_t r = blockIdx.x * (MIP_BLOCK / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     if (r >= a.n_rays) return;
-    const float dx = a.rays_d[r * 3ull], dy = a.rays_d[r * 3ull + 1], dz = a.rays_d[r * 3ull + 2];
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
+    MipRender p{a, 0.f};
+    p.ray(r);
     const float g[3] = {grad_rgb[r * 3ull], grad_rgb[r * 3ull + 1], grad_rgb[r * 3ull + 2]};
     const float white = a.white_bkgd ? 1.f : 0.f;
     // pass 1: total = sum_i w_i gc_i
-    double carry = 0.0, total = 0.0;
-    for (uint32_t base = 0; base < a.n_s; base += 64) {
-        const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        MipSample s;
-        double dd = 0.0, wg = 0.0;
-        if (live) { s = mip_load_sample(a, r, i, dnorm); dd = (double)s.dd; }
-        const double incl = xr_wave_incl_sum(dd);
-        if (live) {
-            const float before = (float)(carry + (incl - dd));
-            const float w = (1.f - expf(-s.dd)) * expf(-before);
-            float gc = 0.f;
-            for (int c = 0; c < 3; ++c) gc += g[c] * (s.rgb[c] - white);
-            wg = (double)w * (double)gc;
-        }
-        total += xr_wave_sum(wg);
-        carry += __shfl(incl, 63, 64);
-    }
+    double total = 0.0;
+    XrCumsumStep st;
+    for (uint32_t base = 0; base < a.n_s; base += 64) total += xr_wave_sum(xr_render_term(p, st, r, base + lane, g, white).wg);
     // pass 2: gradients
-    carry = 0.0;
+    st = XrCumsumStep();
     double carry_wg = 0.0;
     for (uint32_t base = 0; base < a.n_s; base += 64) {
         const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        MipSample s;
-        double dd = 0.0, wg = 0.0;
-        float w = 0.f, gc = 0.f, before = 0.f;
-        if (live) { s = mip_load_sample(a, r, i, dnorm); dd = (double)s.dd; }
-        const double incl = xr_wave_incl_sum(dd);
-        if (live) {
-            before = (float)(carry + (incl - dd));
-            w = (1.f - expf(-s.dd)) * expf(-before);
-            for (int c = 0; c < 3; ++c) gc += g[c] * (s.rgb[c] - white);
-            wg = (double)w * (double)gc;
-        }
-        const double incl_wg = xr_wave_incl_sum(wg);
-        if (live) {
+        const XrRenderTerm<MipRender> q = xr_render_term(p, st, r, i, g, white);
+        const MipSample& s = q.s;
+        const double incl_wg = xr_wave_incl_sum(q.wg);
+        if (i < a.n_s) {
             const double suffix = total - (carry_wg + incl_wg);
-            const float t_next = expf(-before) * expf(-s.dd);           // T_{k+1}
-            const float d_dd = (float)((double)(t_next * gc) - suffix);
+            const float t_next = expf(-q.t) * expf(-s.dd);              // T_{k+1}; q.t is the exclusive cumsum of density_delta
+            const float d_dd = (float)((double)(t_next * q.gc) - suffix);
             float4 o;
             const float k = 1.f + 2.f * a.rgb_padding;
-            o.x = g[0] * w * (s.sg[0] * (1.f - s.sg[0])) * k;
-            o.y = g[1] * w * (s.sg[1] * (1.f - s.sg[1])) * k;
-            o.z = g[2] * w * (s.sg[2] * (1.f - s.sg[2])) * k;
+            o.x = g[0] * q.w * (s.sg[0] * (1.f - s.sg[0])) * k;
+            o.y = g[1] * q.w * (s.sg[1] * (1.f - s.sg[1])) * k;
+            o.z = g[2] * q.w * (s.sg[2] * (1.f - s.sg[2])) * k;
             o.w = d_dd * s.dist * xr_mip_density_dact(s.x, a.relu);
             reinterpret_cast<float4*>(grad_raw)[(uint64_t)r * a.n_s + i] = o;
         }
-        carry += __shfl(incl, 63, 64);
         carry_wg += __shfl(incl_wg, 63, 64);
     }
 }

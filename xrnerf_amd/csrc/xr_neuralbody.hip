@@ -15,6 +15,7 @@
 //   k_nb_sample_bwd the same walk, adding w g to the rows in 64-bit fixed point (integer adds commute: repeatable bits)
 // Compiled with -ffp-contract=off: every expression is fp32 in the written order.
 #include "xr_common.h"
+#include "xr_wave.h"
 #include "../../include/xrnerf_mi355_neuralbody.h"
 
 #define NB_BLOCK 256
@@ -110,8 +111,7 @@ __global__ void __launch_bounds__(NB_BLOCK) k_nb_count(const int32_t* __restrict
         const uint32_t cell = base + s * NB_BLOCK + threadIdx.x;
         if (cell < cells && vol[cell] == NB_MARK) ++c;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    c = xr_wave_sum(c);
     if (lane == 0) s_c[wave] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -130,12 +130,7 @@ __global__ void __launch_bounds__(NB_BLOCK) k_nb_scan(const uint32_t* __restrict
     for (uint32_t b0 = 0; b0 < nb; b0 += NB_BLOCK) {
         const uint32_t b = b0 + t;
         const uint32_t c = b < nb ? cnt[b] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += v;
-        }
+        const uint32_t incl = xr_wave_incl_sum(c);
         __syncthreads();                                           // s_w of the previous sweep has been read
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();

@@ -4,19 +4,20 @@
 //   k_nerf_encode        workgroup = 64 consecutive rows.  The lanes sweep (row, frequency, axis) items -- one exact scaling, one sinf and
 //                        one cosf each -- into an LDS tile; the direction features are computed once per direction of the tile; the tile
 //                        (padding columns as zeros) then leaves as one contiguous, coalesced block of ld floats per row
-//   k_nerf_render_fwd    wave = ray, 64 samples per sweep; transmittance as an fp64 prefix PRODUCT of (1 - alpha + 1e-10) (the arithmetic
-//                        of the inference kernel k_nerf_render, xr_kilo.hip), fixed-order butterflies for the sums
+//   k_nerf_render_fwd    wave = ray, 64 samples per sweep: the forward sweep of xr_render.h with the policy VnRender; transmittance as an
+//                        fp64 prefix PRODUCT of (1 - alpha + 1e-10) (the arithmetic of the inference kernel k_nerf_render, xr_kilo.hip)
 //   k_nerf_render_bwd    wave = ray; dL/draw from dL/drgb without a division: with G_k = sum_c g_c rgb_kc - [white] sum_c g_c and the
 //                        reverse recurrence S_{k-1} = alpha_k G_k + f_k S_k (S_last = 0, f = 1 - alpha + 1e-10),
 //                        dL/dalpha_k = T_k (G_k - S_k).  The recurrence is an affine map per sample; the wave composes them with a reverse
-//                        Hillis-Steele scan in fp64, sweeps taken from the last to the first
+//                        Hillis-Steele scan in fp64, sweeps taken from the last to the first (kept apart from the two-pass backward of
+//                        xr_mip.hip / xr_bungee.hip: xr_render.h says why)
 //   k_nerf_sample_pdf    wave = ray; cdf over the bin midpoints (fp64 scan) in LDS, one binary search per draw, then a bitonic sort of
 //                        [z_vals | z_samples] in LDS and pts = o + d z
 // No atomics anywhere, every reduction / scan has a fixed order: the same input gives the same bits on every launch.
 // Compiled with -ffp-contract=off: every expression is fp32 in the reference's operation order.
 #include "xr_common.h"
 #include "xr_mip_math.h"
-#include "xr_wave.h"
+#include "xr_render.h"
 #include "../../include/xrnerf_mi355_vanilla.h"
 
 #define VN_BLOCK 256
@@ -104,43 +105,26 @@ static __device__ inline float vn_dnorm(const VnRenderArgs& a, uint32_t r) {
     return sqrtf(dx * dx + dy * dy + dz * dz);
 }
 
+// the forward sweep's policy (xr_render.h)
+struct VnRender {
+    typedef VnSample Sample;
+    typedef XrCumprodStep Step;
+    VnRenderArgs a;
+    float dnorm;
+    __device__ void ray(uint32_t r) { dnorm = vn_dnorm(a, r); }
+    __device__ VnSample load(uint32_t r, uint32_t i) const { return vn_load(a, r, i, dnorm); }
+    __device__ double step_in(const VnSample& s) const { return (double)s.f; }
+    __device__ float weight(const VnSample& s, float t) const { return s.alpha * t; }
+    __device__ void colours(const VnSample& s, float* c) const {
+        c[0] = xr_mip_sigmoid(s.v.x); c[1] = xr_mip_sigmoid(s.v.y); c[2] = xr_mip_sigmoid(s.v.z);
+    }
+    __device__ float depth(const VnSample& s) const { return s.z; }
+    __device__ float ray_scalar(uint32_t, float depth, float acc) const { return xr_render_disp(depth, acc); }
+};
+
 __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_fwd(VnRenderArgs a, float* __restrict__ rgb_out, float* __restrict__ disp_out,
                                                               float* __restrict__ acc_out, float* __restrict__ weights_out) {
-    const uint32_t r = blockIdx.x * VN_WAVES + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    if (r >= a.n_rays) return;                 // whole waves leave together
-    const float dnorm = vn_dnorm(a, r);
-    double carry = 1.0;                        // prod of (1 - alpha + 1e-10) over the samples before this sweep
-    float a_c[3] = {0.f, 0.f, 0.f}, a_w = 0.f, a_z = 0.f;
-    for (uint32_t base = 0; base < a.n_s; base += 64) {
-        const uint32_t i = base + lane;
-        const bool live = i < a.n_s;
-        VnSample s;
-        double f = 1.0;
-        if (live) { s = vn_load(a, r, i, dnorm); f = (double)s.f; }
-        const double incl = xr_wave_incl_prod(f);
-        const double excl = xr_wave_excl_of_prod(incl);                    // all lanes take part in the shuffle
-        if (live) {
-            const float w = s.alpha * (float)(carry * excl);
-            weights_out[(uint64_t)r * a.n_s + i] = w;
-            a_w += w;
-            a_z += w * s.z;
-            a_c[0] += w * xr_mip_sigmoid(s.v.x);
-            a_c[1] += w * xr_mip_sigmoid(s.v.y);
-            a_c[2] += w * xr_mip_sigmoid(s.v.z);
-        }
-        carry *= __shfl(incl, 63, 64);
-    }
-    const float acc = xr_wave_sum(a_w), depth = xr_wave_sum(a_z);
-    float col[3];
-    for (int c = 0; c < 3; ++c) col[c] = xr_wave_sum(a_c[c]);
-    if (lane == 0) {
-        const float q = depth / acc;
-        const float m = (q != q) ? q : fmaxf(1e-10f, q);                   // torch.max propagates the NaN of 0/0
-        disp_out[r] = 1.f / m;
-        acc_out[r] = acc;
-        for (int c = 0; c < 3; ++c) rgb_out[r * 3ull + c] = a.white_bkgd ? col[c] + (1.f - acc) : col[c];
-    }
+    xr_render_fwd(VnRender{a, 0.f}, blockIdx.x * VN_WAVES + (threadIdx.x >> 6), rgb_out, disp_out, acc_out, weights_out);
 }
 
 __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_bwd(VnRenderArgs a, const float* __restrict__ grad_rgb,
@@ -155,14 +139,13 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_bwd(VnRenderArgs a, co
     // pass 1 (only with more than one sweep): lane b keeps the transmittance in front of sweep b
     double my_carry = 1.0;
     if (n_sweeps > 1) {
-        double carry = 1.0;
+        XrCumprodStep st;
         for (uint32_t b = 0; b + 1 < n_sweeps; ++b) {
-            if (lane == b) my_carry = carry;
+            if (lane == b) my_carry = st.carry;
             const uint32_t i = b * 64 + lane;                                // a full sweep: every lane is live
-            const double incl = xr_wave_incl_prod((double)vn_load(a, r, i, dnorm).f);
-            carry *= __shfl(incl, 63, 64);
+            st.step64((double)vn_load(a, r, i, dnorm).f);
         }
-        if (lane == n_sweeps - 1) my_carry = carry;
+        if (lane == n_sweeps - 1) my_carry = st.carry;
     }
     // pass 2, last sweep first: S_carry is S at the last sample of the sweep
     double s_carry = 0.0;
@@ -179,16 +162,12 @@ __global__ void __launch_bounds__(VN_BLOCK) k_nerf_render_bwd(VnRenderArgs a, co
             G = ((g[0] * sg[0] + g[1] * sg[1]) + g[2] * sg[2]) - gw;
             ag = (double)s.alpha * (double)G;
         }
-        const double incl = xr_wave_incl_prod(f);
-        const double excl = xr_wave_excl_of_prod(incl);
-        const double T = __shfl(my_carry, (int)b, 64) * excl;
-        // reverse inclusive scan of the maps x -> ag + f x: (F, A) of lane k covers samples k .. min(k + 2 off - 1, 63)
-        double F = f, A = ag;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double Fo = __shfl_down(F, off, 64), Ao = __shfl_down(A, off, 64);
-            if (lane + off < 64) { A = A + F * Ao; F = F * Fo; }
-        }
+        XrCumprodStep st;
+        st.carry = __shfl(my_carry, (int)b, 64);                             // the transmittance in front of this sweep, from pass 1
+        const double T = st.step64(f);
+        // reverse inclusive scan of the maps x -> ag + f x: (F, A) of lane k covers samples k .. 63
+        const XrAffine<double> m = xr_wave_affine_rscan(f, ag);
+        const double F = m.F, A = m.A;
         // S_k = the map of samples k+1 .. 63 applied to the carry
         const double Fn = __shfl_down(F, 1, 64), An = __shfl_down(A, 1, 64);
         const double S = lane == 63 ? s_carry : An + Fn * s_carry;

@@ -16,6 +16,7 @@ from torch import nn
 from . import builder, ops
 from .builder import EMBEDDERS, NETWORKS, RENDERS
 from .networks import get_dist_info, mse2psnr, unfold_batching
+from .renders import RayRender
 from .vanilla import NerfNetwork, merge_ret
 
 
@@ -108,25 +109,6 @@ class MipNerfEmbedder(nn.Module):
         return data
 
 
-class _MipRenderFn(torch.autograd.Function):
-    """renderer forward / backward as one launch each; gradients flow from the colours only (the reference's losses,
-    networks/mipnerf.py:52-60; `weights` feed the detached resampler)"""
-
-    @staticmethod
-    def forward(ctx, raw, z_vals, rays_d, density_bias, rgb_padding, white_bkgd, act):
-        rgb, dist, acc, w = ops.mip_render_forward(raw, z_vals, rays_d, density_bias, rgb_padding, white_bkgd, act)
-        ctx.save_for_backward(raw, z_vals, rays_d)
-        ctx.cfg = (density_bias, rgb_padding, white_bkgd, act)
-        ctx.mark_non_differentiable(dist, acc, w)
-        return rgb, dist, acc, w
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_dist, g_acc, g_w):
-        raw, z_vals, rays_d = ctx.saved_tensors
-        return (ops.mip_render_backward(raw, z_vals, rays_d, g_rgb.contiguous(), *ctx.cfg), None, None, None, None,
-                None, None)
-
-
 @RENDERS.register_module()
 class MipNerfRender(nn.Module):
     """NerfRender.forward with MipNerfRender's weights / distance map (nerf_render.py:45-98, mipnerf_render.py:12-33)"""
@@ -147,8 +129,9 @@ class MipNerfRender(nn.Module):
         if noise_std > 0.:
             noise = torch.randn(raw[..., 3].shape, device=raw.device) * noise_std
             raw = torch.cat([raw[..., :3], (raw[..., 3] + noise)[..., None]], -1)
-        rgb, dist, acc, w = _MipRenderFn.apply(raw, z_vals, data['rays_d'], float(self.density_bias),
-                                               float(self.rgb_padding), bool(self.white_bkgd), self.density_activation)
+        rgb, dist, acc, w = RayRender.apply(ops.mip_render_forward, ops.mip_render_backward, raw, z_vals, data['rays_d'], None,
+                                            float(self.density_bias), float(self.rgb_padding), bool(self.white_bkgd),
+                                            self.density_activation)
         data['weights'] = w
         return data, {'rgb': rgb, 'disp': dist, 'acc': acc}
 

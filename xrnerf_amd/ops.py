@@ -1138,17 +1138,29 @@ def mip_encode_gaussians(means, covs, viewdirs, min_deg, max_deg, min_deg_view, 
 _MIP_ACT = {'softplus': 0, 'relu': 1}
 
 
+def _render_outputs(R, S, dev):
+    """what every dense renderer's forward writes: rgb [R,3], the ray's scalar (disparity or distance) [R], acc [R], weights [R,S]"""
+    return (torch.empty((R, 3), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.float32, device=dev),
+            torch.empty((R,), dtype=torch.float32, device=dev), torch.empty((R, S), dtype=torch.float32, device=dev))
+
+
+def _render_noise(noise, R, S):
+    """the optional density noise of the vanilla and Bungee renderers: float32, contiguous, one value per sample"""
+    if noise is None:
+        return None
+    noise = _f32c(noise)
+    if tuple(noise.shape) != (R, S):
+        raise _lib.XrError('noise must be [R, S]')
+    return noise
+
+
 def mip_render_forward(raw, z_vals, rays_d, density_bias, rgb_padding, white_bkgd, density_activation='softplus'):
     """-> rgb [R,3], distance [R], acc [R], weights [R,S]"""
     L = _lib.load()
     R, n_z = z_vals.shape
-    dev = raw.device
     raw = _f32c(raw)
     assert tuple(raw.shape) == (R, n_z - 1, 4), 'raw must be [R, n_z-1, 4] (rgb + density)'
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    dist = torch.empty((R,), dtype=torch.float32, device=dev)
-    acc = torch.empty((R,), dtype=torch.float32, device=dev)
-    w = torch.empty((R, n_z - 1), dtype=torch.float32, device=dev)
+    rgb, dist, acc, w = _render_outputs(R, n_z - 1, raw.device)
     with _span('xr_mip_render_forward', R * (n_z - 1)):
         _lib.check(L.xr_mip_render_forward(_ptr(raw), _ptr(_f32c(z_vals)), _ptr(_f32c(rays_d)), R, n_z,
                                            float(density_bias), float(rgb_padding), int(bool(white_bkgd)),
@@ -1309,11 +1321,7 @@ def nerf_render_forward(raw, z_vals, rays_d, white_bkgd):
     raw, z_vals = _f32c(raw), _f32c(z_vals)
     R, S = z_vals.shape
     assert tuple(raw.shape) == (R, S, 4)
-    dev = raw.device
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((R,), dtype=torch.float32, device=dev)
-    acc = torch.empty((R,), dtype=torch.float32, device=dev)
-    w = torch.empty((R, S), dtype=torch.float32, device=dev)
+    rgb, disp, acc, w = _render_outputs(R, S, raw.device)
     with _span('xr_nerf_render_forward', R * S):
         _lib.check(L.xr_nerf_render_forward(_ptr(raw), _ptr(z_vals), _ptr(_f32c(rays_d)), R, S, int(bool(white_bkgd)),
                                             _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(w), _stream()), 'xr_nerf_render_forward')
@@ -1549,21 +1557,14 @@ def _bungee_render_common(raw, z_vals, viewdirs, noise):
     raw = _f32c(raw)
     if raw.dim() != 4 or tuple(raw.shape[:2]) != (R, n_z - 1) or raw.shape[3] != 4:
         raise _lib.XrError('raw must be [R, n_z-1, heads, 4]')
-    if noise is not None:
-        noise = _f32c(noise)
-        assert tuple(noise.shape) == (R, n_z - 1)
-    return raw, _f32c(z_vals), _f32c(viewdirs), noise, R, n_z, raw.shape[2]
+    return raw, _f32c(z_vals), _f32c(viewdirs), _render_noise(noise, R, n_z - 1), R, n_z, raw.shape[2]
 
 
 def bungee_render_forward(raw, z_vals, viewdirs, stage, density_bias=-1.0, rgb_padding=0.0, white_bkgd=False,
                           density_activation='softplus', noise=None):
     """BungeeNerfRender.forward: raw [R,S,H,4] -> rgb [R,3], disp [R], acc [R], weights [R,S]"""
     raw, z_vals, viewdirs, noise, R, n_z, H = _bungee_render_common(raw, z_vals, viewdirs, noise)
-    dev = raw.device
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((R,), dtype=torch.float32, device=dev)
-    acc = torch.empty((R,), dtype=torch.float32, device=dev)
-    w = torch.empty((R, n_z - 1), dtype=torch.float32, device=dev)
+    rgb, disp, acc, w = _render_outputs(R, n_z - 1, raw.device)
     with _span('xr_bungee_render_forward', R * (n_z - 1)):
         _lib.check(_lib.load().xr_bungee_render_forward(_ptr(raw), _ptr(z_vals), _ptr(viewdirs), _ptr(noise), R, n_z, H, int(stage),
                                                         float(density_bias), float(rgb_padding), int(bool(white_bkgd)),
@@ -1622,21 +1623,13 @@ def _nerf_render_common(raw, z_vals, rays_d, noise):
     R, S = z_vals.shape
     if tuple(raw.shape) != (R, S, 4) or tuple(rays_d.shape) != (R, 3):
         raise _lib.XrError('the NeRF renderer takes raw [R, S, 4], z_vals [R, S] and rays_d [R, 3]')
-    if noise is not None:
-        noise = _f32c(noise)
-        if tuple(noise.shape) != (R, S):
-            raise _lib.XrError('noise must be [R, S]')
-    return raw, z_vals, rays_d, noise, R, S
+    return raw, z_vals, rays_d, _render_noise(noise, R, S), R, S
 
 
 def nerf_render_train_forward(raw, z_vals, rays_d, white_bkgd, noise=None):
     """NerfRender.forward (relu density, no padding, no bias) with the optional density noise: -> rgb [R,3], disp [R], acc [R], weights [R,S]"""
     raw, z_vals, rays_d, noise, R, S = _nerf_render_common(raw, z_vals, rays_d, noise)
-    dev = raw.device
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((R,), dtype=torch.float32, device=dev)
-    acc = torch.empty((R,), dtype=torch.float32, device=dev)
-    w = torch.empty((R, S), dtype=torch.float32, device=dev)
+    rgb, disp, acc, w = _render_outputs(R, S, raw.device)
     with _span('xr_nerf_render_train_forward', R * S):
         _lib.check(_lib.load().xr_nerf_render_train_forward(_ptr(raw), _ptr(z_vals), _ptr(rays_d), _ptr(noise), R, S, int(bool(white_bkgd)),
                                                             _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(w), _stream()),

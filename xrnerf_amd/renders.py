@@ -54,6 +54,32 @@ class _Composite(torch.autograd.Function):
         return d_raw, None, None
 
 
+def _noise_kw(noise):
+    """(the Mip-NeRF ops take no noise: their module adds it to raw)"""
+    return {} if noise is None else {'noise': noise}
+
+
+class RayRender(torch.autograd.Function):
+    """The dense renderers' autograd node (NerfRender, MipNerfRender, BungeeNerfRender): one launch forward (`fwd`), one backward
+    (`bwd`), a pair of ops taking (raw, z_vals, dirs, [grad_rgb,] *cfg, noise=...).  Gradients flow from the colours only -- all the
+    reference's losses read (networks/nerf.py:71-92, mipnerf.py:52-60); the second output, acc and the weights (which feed the
+    detached resampler) are marked non-differentiable rather than silently given a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, fwd, bwd, raw, z_vals, dirs, noise, *cfg):
+        rgb, scalar, acc, w = fwd(raw, z_vals, dirs, *cfg, **_noise_kw(noise))
+        ctx.save_for_backward(raw, z_vals, dirs, noise)
+        ctx.bwd, ctx.cfg = bwd, cfg
+        ctx.mark_non_differentiable(scalar, acc, w)
+        return rgb, scalar, acc, w
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_scalar, g_acc, g_w):
+        raw, z_vals, dirs, noise = ctx.saved_tensors
+        g = ctx.bwd(raw, z_vals, dirs, g_rgb.contiguous(), *ctx.cfg, **_noise_kw(noise))
+        return (None, None, g) + (None,) * (3 + len(ctx.cfg))
+
+
 def composite_test(raw, m, bg_color):
     """K5 (calc_rgb.cu:144-206): colour + alpha per ray against a constant background read on the host (like the reference's
     `bg_color_cpu`, calc_rgb.cu:366,378)"""

@@ -4,7 +4,7 @@
 This is the reference's only renderer that runs on a CPU as shipped and is
 pure PyTorch there.  Host tensors take plain tensor code (the CPU-runnable parity case).  On the device a training step is
   encode (xr_nerf_encode) -> the MLP as ONE autograd node over the linear kernels (_NerfMlpFn) -> renderer forward / backward
-  (xr_nerf_render_train_forward / xr_nerf_render_backward, _NerfRenderFn) -> resampling + merge + points (xr_nerf_sample_pdf)
+  (xr_nerf_render_train_forward / xr_nerf_render_backward, renders.RayRender) -> resampling + merge + points (xr_nerf_sample_pdf)
 and the same again for the fine network (xrnerf_amd/csrc/xr_vanilla.hip; DESIGN.md "Vanilla NeRF (config #1)").  Constructor signatures, `data` dict keys,
 sub-module / parameter names (`pts_linears.N`, `views_linears.0`, `feature_linear`, `alpha_linear`,
 `rgb_linear`) and numerics follow
@@ -19,6 +19,7 @@ from torch import nn
 from . import builder
 from .builder import EMBEDDERS, MLPS, NETWORKS, RENDERS
 from .networks import BaseNerfNetwork, img2mse, mse2psnr, unfold_batching
+from .renders import RayRender
 
 
 # ------------------------------------------------------------------ positional encoding
@@ -230,27 +231,6 @@ class _NerfMlpFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------ classic volume rendering
-class _NerfRenderFn(torch.autograd.Function):
-    """NerfRender.forward for training as one launch forward and one backward (xr_nerf_render_train_forward / xr_nerf_render_backward).
-    Gradients flow from the colours only -- all the reference's loss reads (networks/nerf.py:71-92); disp, acc and the weights (which
-    feed the detached resampler) are marked non-differentiable rather than silently given a zero gradient."""
-
-    @staticmethod
-    def forward(ctx, raw, z_vals, rays_d, noise, white_bkgd):
-        from . import ops
-        rgb, disp, acc, w = ops.nerf_render_train_forward(raw, z_vals, rays_d, white_bkgd, noise)
-        ctx.save_for_backward(raw, z_vals, rays_d, noise)
-        ctx.white_bkgd = white_bkgd
-        ctx.mark_non_differentiable(disp, acc, w)
-        return rgb, disp, acc, w
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_disp, g_acc, g_w):
-        from . import ops
-        raw, z_vals, rays_d, noise = ctx.saved_tensors
-        return ops.nerf_render_backward(raw, z_vals, rays_d, g_rgb, ctx.white_bkgd, noise), None, None, None, None
-
-
 @RENDERS.register_module()
 class NerfRender(nn.Module):
     def __init__(self, white_bkgd=False, raw_noise_std=0, rgb_padding=0, density_bias=0, density_activation='relu',
@@ -287,9 +267,10 @@ class NerfRender(nn.Module):
                 and raw.dim() == 3 and raw.shape[-1] == 4 and raw.shape[0] > 0 and 1 <= raw.shape[1] <= 4096
                 and tuple(z_vals.shape) == tuple(raw.shape[:2]) and tuple(rays_d.shape) == (raw.shape[0], 3)
                 and not z_vals.requires_grad and not rays_d.requires_grad and ops.vanilla_kernels_available()):
-            # training on the device: one launch forward, one backward (_NerfRenderFn); gradients flow from the colours
+            # training on the device: one launch forward, one backward (renders.RayRender); gradients flow from the colours
             noise = torch.randn(raw.shape[:2], device=raw.device) * noise_std if noise_std > 0. else None
-            rgb_map, disp, acc, weights = _NerfRenderFn.apply(raw, z_vals, rays_d, noise, bool(self.white_bkgd))
+            rgb_map, disp, acc, weights = RayRender.apply(ops.nerf_render_train_forward, ops.nerf_render_backward, raw, z_vals, rays_d,
+                                                          noise, bool(self.white_bkgd))
             data['weights'] = weights
             return data, {'rgb': rgb_map, 'disp': disp, 'acc': acc}
         if (raw.is_cuda and not (torch.is_grad_enabled() and raw.requires_grad) and noise_std == 0
