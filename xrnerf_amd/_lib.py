@@ -232,6 +232,19 @@ GNR_RENDER_SIGNATURES = {
     'xr_gnr_composite_backward': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp]),
 }
 
+# GNR image encoder (csrc/xr_gnr_encoder.hip, declared in include/xrnerf_mi355_gnr_encoder.h): a table of its own as well
+GNR_ENCODER_SIGNATURES = {
+    'xr_hg_conv2d': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _i32, _vp, _u32, _vp]),
+    'xr_hg_gn_stats_workspace_bytes': (_sz, [_u32, _u32, _u32]),
+    'xr_hg_gn_stats': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _f, _vp, _vp, _vp, _sz, _vp]),
+    'xr_hg_gn_relu': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    'xr_hg_avgpool2': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
+    'xr_hg_bicubic_up2': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    'xr_hg_add': (_i32, [_vp, _u32, _u64, _u32, _vp, _u32, _vp]),
+    'xr_hg_conv_block_workspace_bytes': (_sz, [_u32, _u32, _u32]),
+    'xr_hg_conv_block': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32] + [_vp] * 12 + [_u32, _f, _vp, _u32, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -288,7 +301,8 @@ def load():
                     fcntl.flock(lock, fcntl.LOCK_UN)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
-            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()):
+            list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
+            list(GNR_ENCODER_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

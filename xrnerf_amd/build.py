@@ -51,6 +51,9 @@ SOURCES = {
     # pixel of a projected coordinate and the gather's corner a floorf of one, so the projection must round like its un-fused fp32
     # tensor-op restatement
     'xr_gnr_render.hip': ['-ffp-contract=off'],
+    # GNR image encoder (hourglass convolutions on the fp32 MFMA, GroupNorm statistics, pool, bicubic upsampling): the only index
+    # decision on a float is the bicubic tap, the floor of ONE product (scale * dst), which contraction cannot change: contraction stays on
+    'xr_gnr_encoder.hip': [],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

@@ -2236,3 +2236,151 @@ def gnr_composite_backward(net, source_rgb, idx, table, t_vals, noise, white, d_
         _lib.check(_lib.load().xr_gnr_composite_backward(*head, int(bool(white)), _ptr(d_rgb_map), _ptr(trans), _ptr(d_net), _stream()),
                                                          'xr_gnr_composite_backward')
     return d_net
+
+
+# ---------------------------------------------------------------- GNR image encoder (csrc/xr_gnr_encoder.hip)
+def gnr_encoder_kernels_available():
+    """the loaded library handle has xr_gnr_encoder.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_hg_conv2d')
+
+
+def _hg_map(t, what):
+    """a channel-last map [N,H,W,C], or a column slice of one (`buf[..., a:b]`) -> (pointer of its channel 0, row stride)"""
+    if not _on_device(t):
+        raise _lib.XrError('xrnerf_amd ops need ROCm device tensors (got a %s tensor): there is no CPU fallback' % t.device)
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError('%s must be a float32 [N, H, W, C] map' % what)
+    N, H, W, Cc = t.shape
+    ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if N > 1 else Cc))
+    if (Cc > 1 and t.stride(3) != 1) or ld < Cc or (W > 1 and H > 1 and t.stride(1) != W * ld) or (N > 1 and t.stride(0) != H * W * ld):
+        raise ValueError('%s must be a channel-last map or a column slice of one (strides %r)' % (what, t.stride()))
+    return C.c_void_p(t.data_ptr()), int(ld)
+
+
+def hg_relay_weight(w):
+    """nn.Conv2d.weight [Cout, Cin, k, k] -> the kernel's [k k Cin, Cout] (once per load, not per call)"""
+    return w.detach().permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous().float()
+
+
+def hg_conv2d(x, w_kc, ksize, stride=1, norm=None, bias=None, relu=False, out=None, accumulate=False):
+    """x [N,H,W,Cin] (map or column slice), w_kc = hg_relay_weight(weight); norm = (mean [N,G], rstd [N,G], gamma [Cin], beta [Cin]):
+    relu(group_norm(x)) is what the convolution reads, zero padding after it; -> out [N,Ho,Wo,Cout] (map or column slice; with
+    `accumulate` the result is added to what it holds)"""
+    xp, ldx = _hg_map(x, 'x')
+    N, H, W, Cin = x.shape
+    Cout = w_kc.shape[1]
+    if w_kc.shape[0] != ksize * ksize * Cin:
+        raise ValueError('weight %r does not fit k = %d, Cin = %d' % (tuple(w_kc.shape), ksize, Cin))
+    pad = ksize // 2
+    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate needs an output to add to')
+        out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (N, Ho, Wo, Cout):
+        raise ValueError('out must be [%d, %d, %d, %d], got %r' % (N, Ho, Wo, Cout, tuple(out.shape)))
+    yp, ldy = _hg_map(out, 'out')
+    mean = rstd = gamma = beta = None
+    groups = 0
+    if norm is not None:
+        mean, rstd, gamma, beta = norm
+        groups = mean.shape[1]
+    with _span('xr_hg_conv2d', N * Ho * Wo):
+        _lib.check(_lib.load().xr_hg_conv2d(xp, ldx, N, H, W, Cin, _ptr(w_kc), Cout, int(ksize), int(stride), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                            _ptr(beta), groups, _ptr(bias), int(bool(relu)), int(bool(accumulate)), yp, ldy, _stream()), 'xr_hg_conv2d')
+    return out
+
+
+def hg_gn_stats(x, groups=32, eps=1e-5):
+    """x [N,H,W,C] (map or column slice) -> (mean, rstd) [N, groups] of GroupNorm(groups, C): biased variance, fixed summation order"""
+    xp, ldx = _hg_map(x, 'x')
+    N, H, W, Cc = x.shape
+    lib = _lib.load()
+    mean = torch.empty((N, groups), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((N, groups), dtype=torch.float32, device=x.device)
+    ws = _ws(x.device, int(lib.xr_hg_gn_stats_workspace_bytes(N, H * W, groups)) + 16, 'hg_gn_stats')
+    off = (-ws.data_ptr()) % 16
+    with _span('xr_hg_gn_stats', N * H * W):
+        _lib.check(lib.xr_hg_gn_stats(xp, ldx, N, H * W, Cc, groups, float(eps), _ptr(mean), _ptr(rstd), C.c_void_p(ws.data_ptr() + off),
+                                      ws.numel() - off, _stream()), 'xr_hg_gn_stats')
+    return mean, rstd
+
+
+def hg_gn_relu(x, mean, rstd, gamma, beta, out=None):
+    """relu(group_norm(x)) from hg_gn_stats' statistics; out=x works in place"""
+    xp, ldx = _hg_map(x, 'x')
+    N, H, W, Cc = x.shape
+    if out is None:
+        out = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device)
+    yp, ldy = _hg_map(out, 'out')
+    if out.shape != x.shape:
+        raise ValueError('out must have the shape of x')
+    with _span('xr_hg_gn_relu', N * H * W):
+        _lib.check(_lib.load().xr_hg_gn_relu(xp, ldx, N, H * W, Cc, mean.shape[1], _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), yp, ldy,
+                                             _stream()), 'xr_hg_gn_relu')
+    return out
+
+
+def hg_avgpool2(x, out=None):
+    """F.avg_pool2d(., 2, stride=2) on a channel-last map"""
+    xp, ldx = _hg_map(x, 'x')
+    N, H, W, Cc = x.shape
+    if out is None:
+        out = torch.empty((N, H // 2, W // 2, Cc), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (N, H // 2, W // 2, Cc):
+        raise ValueError('out must be [N, H / 2, W / 2, C]')
+    yp, ldy = _hg_map(out, 'out')
+    with _span('xr_hg_avgpool2', N * H * W):
+        _lib.check(_lib.load().xr_hg_avgpool2(xp, ldx, N, H, W, Cc, yp, ldy, _stream()), 'xr_hg_avgpool2')
+    return out
+
+
+def hg_bicubic_up2(x, addend=None, out=None):
+    """F.interpolate(., scale_factor=2, mode='bicubic', align_corners=True) on a channel-last map (+ addend; out=addend works in place)"""
+    xp, ldx = _hg_map(x, 'x')
+    N, H, W, Cc = x.shape
+    if out is None:
+        out = torch.empty((N, 2 * H, 2 * W, Cc), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (N, 2 * H, 2 * W, Cc) or (addend is not None and addend.shape != out.shape):
+        raise ValueError('out and addend must be [N, 2 H, 2 W, C]')
+    yp, ldy = _hg_map(out, 'out')
+    ap, lda = _hg_map(addend, 'addend') if addend is not None else (None, 0)
+    with _span('xr_hg_bicubic_up2', N * H * W * 4):
+        _lib.check(_lib.load().xr_hg_bicubic_up2(xp, ldx, N, H, W, Cc, ap, lda, yp, ldy, _stream()), 'xr_hg_bicubic_up2')
+    return out
+
+
+def hg_add(x, out):
+    """out += x on channel-last maps (or column slices) of one shape"""
+    xp, ldx = _hg_map(x, 'x')
+    yp, ldy = _hg_map(out, 'out')
+    if out.shape != x.shape:
+        raise ValueError('out must have the shape of x')
+    N, H, W, Cc = x.shape
+    with _span('xr_hg_add', N * H * W):
+        _lib.check(_lib.load().xr_hg_add(xp, ldx, N * H * W, Cc, yp, ldy, _stream()), 'xr_hg_add')
+    return out
+
+
+def hg_conv_block(x, weights, norms, out=None, groups=32, eps=1e-5):
+    """one ConvBlock in one call: x [N,H,W,Cin]; weights = (w1, w2, w3, w_down or None), re-laid (hg_relay_weight); norms = the gamma and
+    beta of bn1, bn2, bn3 and bn4 (eight tensors; bn4's are read with w_down only) -> out [N,H,W,Cout] = cat(out1, out2, out3) + residual"""
+    xp, ldx = _hg_map(x, 'x')
+    N, H, W, Cin = x.shape
+    w1, w2, w3, wd = weights
+    Cout = 2 * w1.shape[1]
+    if out is None:
+        out = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (N, H, W, Cout):
+        raise ValueError('out must be [%d, %d, %d, %d], got %r' % (N, H, W, Cout, tuple(out.shape)))
+    if w1.shape[0] != 9 * Cin or tuple(w2.shape) != (9 * (Cout // 2), Cout // 4) or tuple(w3.shape) != (9 * (Cout // 4), Cout // 4) or \
+            (wd is not None and tuple(wd.shape) != (Cin, Cout)):
+        raise ValueError('the weights do not fit a ConvBlock(%d, %d)' % (Cin, Cout))
+    yp, ldy = _hg_map(out, 'out')
+    lib = _lib.load()
+    ws = _ws(x.device, int(lib.xr_hg_conv_block_workspace_bytes(N, H * W, groups)) + 16, 'hg_conv_block')
+    off = (-ws.data_ptr()) % 16
+    with _span('xr_hg_conv_block', N * H * W):
+        _lib.check(lib.xr_hg_conv_block(xp, ldx, N, H, W, Cin, Cout, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(wd), *[_ptr(t) for t in norms], groups, float(eps),
+                                        yp, ldy, C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()), 'xr_hg_conv_block')
+    return out
