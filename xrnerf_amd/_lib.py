@@ -232,6 +232,25 @@ GNR_RENDER_SIGNATURES = {
     'xr_gnr_composite_backward': (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp]),
 }
 
+# GNR mesh reconstruction (csrc/xr_gnr_recon.hip, declared in include/xrnerf_mi355_gnr_recon.h): a table of its own as well
+_GC_GRID = [_vp, _d, _vp, _vp]                              # lin9 (host doubles), spatial_freq, center3, coords
+GNR_RECON_SIGNATURES = {
+    'xr_gnr_recon_hull': (_i32, [_u32] + _GC_GRID + [_vp, _vp, _u32, _u32, _vp, _i32, _i32, _f, _f, _vp, _vp]),
+    'xr_gnr_recon_select_workspace_bytes': (_sz, [_u32, _u32]),
+    'xr_gnr_recon_select_count': (_i32, [_u32, _u32, _vp, _vp, _sz, _vp, _vp]),
+    'xr_gnr_recon_select_write': (_i32, [_u32, _u32] + _GC_GRID + [_vp, _vp, _u32, _u32, _f, _f, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    'xr_gnr_recon_scatter': (_i32, [_vp, _vp, _u32, _i32, _f, _u32, _vp, _vp, _vp]),
+    'xr_gnr_recon_fold_workspace_bytes': (_sz, [_u32, _u32]),
+    'xr_gnr_recon_fold': (_i32, [_u32, _u32, _vp, _vp, _vp, _sz, _vp]),
+    'xr_gnr_recon_surface_workspace_bytes': (_sz, [_u32]),
+    'xr_gnr_recon_surface_count': (_i32, [_vp, _u32, _f, _vp, _sz, _vp, _vp]),
+    'xr_gnr_recon_surface_write': (_i32, [_vp, _u32, _f, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    'xr_gnr_recon_world': (_i32, [_vp, _u32, _u32, _vp, _d, _vp, _vp, _vp, _vp]),
+    'xr_gnr_recon_point_rows': (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    'xr_gnr_recon_smooth_workspace_bytes': (_sz, [_u32, _u32]),
+    'xr_gnr_recon_smooth': (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _i32, _d, _vp, _sz, _vp]),
+}
+
 # GNR image encoder (csrc/xr_gnr_encoder.hip, declared in include/xrnerf_mi355_gnr_encoder.h): a table of its own as well
 GNR_ENCODER_SIGNATURES = {
     'xr_hg_conv2d': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _i32, _vp, _u32, _vp]),
@@ -302,7 +321,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
-            list(GNR_ENCODER_SIGNATURES.items()):
+            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

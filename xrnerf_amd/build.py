@@ -51,6 +51,9 @@ SOURCES = {
     # pixel of a projected coordinate and the gather's corner a floorf of one, so the projection must round like its un-fused fp32
     # tensor-op restatement
     'xr_gnr_render.hip': ['-ffp-contract=off'],
+    # GNR mesh reconstruction (grid hull, octree bookkeeping, iso-surface, Laplacian filter): a grid point is (i step + start) / f + c in
+    # double, rounded once, and must equal numpy's bit for bit -- no fused multiply-add; the projection is the hull's
+    'xr_gnr_recon.hip': ['-ffp-contract=off'],
     # GNR image encoder (hourglass convolutions on the fp32 MFMA, GroupNorm statistics, pool, bicubic upsampling): the only index
     # decision on a float is the bicubic tap, the floor of ONE product (scale * dst), which contraction cannot change: contraction stays on
     'xr_gnr_encoder.hip': [],

@@ -74,7 +74,12 @@ class GnrNetwork(BaseNerfNetwork):
         return rgbs, depths
 
     def reconstruct(self, data):
-        raise NotImplementedError('reconstruct is not built: the renderer has no reconstruct / octree_reconstruct')
+        """-> (verts float64 [Nv,3], faces int32 [T,3], rgbs float32 [Nv,3]): the textured body mesh of the frame"""
+        if data.get('persps') is None:
+            raise NotImplementedError('projection: only the perspective projection is built')
+        with torch.no_grad():
+            data = self.get_image_feature(data)
+            return self.nerf_renderer.reconstruct(**data)
 
     def train_step(self, data, optimizer, **kwargs):
         return self.forward(self.prepare_data(self.cfg, data))

@@ -10,7 +10,8 @@ gnr_render.py:359-526), on the kernels of csrc/xr_gnr_render.hip:
                    reference's -1e4 gives alpha = 0 and a transmittance factor of exactly 1.0f); differentiable in the network output
     synthetic_scene  a small generated scene (body, ring of source cameras, masks, depth maps, maps, rays): the fixture's inputs
 
-    GNRMLP, GnrRenderer   the reference's classes on these stages, registered with the builder
+    GNRMLP, GnrRenderer   the reference's classes on these stages, registered with the builder; reconstruct / octree_reconstruct run on
+                   gnr_recon.py's stages
 
 Device tensors run the kernels; host tensors take the tensor-op path -- the reference's lines restated, which is also the timing
 baseline of tools/microbench_gnr_render.py."""
@@ -711,5 +712,98 @@ class GnrRenderer:
             depths.append(dimg)
         return torch.stack(rgbs, dim=0), torch.stack(depths, dim=0)
 
-    def reconstruct(self, *args, **kwargs):
-        raise NotImplementedError('reconstruct / octree_reconstruct (marching cubes through skimage and trimesh) are not built')
+    # ---- mesh reconstruction (gnr_recon.py)
+    def _network_rows(self, pts, xy, feats_last, images, smpl, mesh_param):
+        """the network's input rows of a chunk of points: mesh queries (set_mesh is the caller's), shape embedding, pixel gather in place
+        into rows -> (emb, rows, source_rgb); feats_last = self._channel_last(feats)"""
+        from .gnr import embed
+        closest_pts, closest_idx = self.mesh_searcher.nearest_points(pts)
+        signs = self.mesh_searcher.inside_mesh(pts) if self.use_smpl_sdf else None
+        emb, _ = embed(pts, closest_pts, closest_idx, signs, smpl, mesh_param, self.width, self.use_nml, self.use_t_pose, self.use_smpl_sdf)
+        col0, ld = self.nerf.row_layout()
+        rows = torch.empty((pts.shape[0], self.num_views, ld), dtype=torch.float32, device=pts.device)
+        rows[:, :, :col0] = torch.cat([self.nerf.pose_embed_fn(emb[:, :3]), emb[:, 3:]], -1)[:, None, :]
+        rows, source_rgb = pixel_gather(xy, feats_last, images[:self.num_views], rows, col0)
+        return emb, rows, source_rgb
+
+    @torch.no_grad()
+    def octree_reconstruct(self, coords, masks, **kwargs):
+        """The reference's signature: coords [N,N,N,3] (array or tensor) or None -- then kwargs['grid'] = (bb_min, bb_max) and the points
+        are made where they are used; masks [V,1,H,W]; kwargs: feats, images, smpl, calibs, mesh_param, persps.  -> the occupancy volume
+        [N,N,N], a float32 tensor that stays on the device (the reference returns a float64 numpy array).  self.recon_levels keeps the
+        number of evaluated points per level."""
+        if kwargs.get('persps') is None:
+            raise NotImplementedError('projection: only the perspective projection is built')
+        from . import gnr_recon as R
+        calibs, persps = kwargs['calibs'][:self.num_views].contiguous(), kwargs['persps'][:self.num_views].contiguous()
+        feats, images, smpl, mesh_param = kwargs['feats'], kwargs['images'], kwargs['smpl'], kwargs['mesh_param']
+        dev, N = calibs.device, self.N_grid
+        if coords is None:
+            bb_min, bb_max = kwargs['grid']
+            grid = R.Grid(N, bb_min, bb_max, mesh_param['spatial_freq'], mesh_param['center'].to(dev))
+        else:
+            grid = R.Grid(N, [0, 0, 0], [1, 1, 1], 1.0, torch.zeros(3, device=dev), torch.as_tensor(np.asarray(coords, dtype=np.float32) if not torch.is_tensor(coords) else coords).to(dev))
+        state = R.grid_hull(grid, calibs, persps, R.dilate_masks(masks[:self.num_views]), self.width, self.height)
+        self.mesh_searcher.set_mesh(smpl['verts'], smpl['faces'])              # once for the whole reconstruction
+
+        feats_last = self._channel_last(feats)
+
+        def evaluate(flat, pts, xy):
+            out = []
+            for i in range(0, pts.shape[0], self.chunk):
+                emb, rows, _ = self._network_rows(pts[i:i + self.chunk], xy[i:i + self.chunk], feats_last, images, smpl, mesh_param)
+                out.append(self.nerf.forward_rows(emb[:, :3], emb[:, 3:], rows, alpha_only=True))
+            return torch.cat(out, 0)
+        select = lambda reso, st: R.level_select(grid, reso, st, calibs, persps, self.width, self.height)
+        vol, _, self.recon_levels = R.octree(N, kwargs.get('reso0', N // 64), state, evaluate, select, gamma=self.gamma)
+        return vol
+
+    @torch.no_grad()
+    def vertex_colours(self, pts, normals, feats, images, calibs, persps, smpl, mesh_param):
+        """the colouring lines of reconstruct: the network at the vertices pts [Nv,3] with the normals as view directions (no smpl_vis),
+        sigmoid of channels 0-2 blended with the source colours by the attention channels -> [Nv,3]"""
+        self.mesh_searcher.set_mesh(smpl['verts'], smpl['faces'])
+        return self._vertex_colours(pts, normals, feats, images, calibs, persps, smpl, mesh_param)
+
+    def _vertex_colours(self, pts, normals, feats, images, calibs, persps, smpl, mesh_param):
+        """vertex_colours on the mesh the searcher already holds (reconstruct: set_mesh once per reconstruction)"""
+        from . import gnr_recon as R
+        V = self.num_views
+        feats_last = self._channel_last(feats)
+        xy, attdirs = R.point_rows(pts.contiguous(), normals.float().contiguous(), calibs, persps, self.width, self.height, smpl['rot'][0] if smpl is not None else None)
+        rgbs = []
+        for i in range(0, pts.shape[0], self.chunk):
+            emb, rows, source_rgb = self._network_rows(pts[i:i + self.chunk], xy[i:i + self.chunk], feats_last, images, smpl, mesh_param)
+            net = self.nerf.forward_rows(emb[:, :3], emb[:, 3:], rows, attdirs[i:i + self.chunk])
+            rgb = torch.sigmoid(net[:, :3])
+            att = net[:, 4:4 + V + 1]
+            rgbs.append(torch.sum(torch.cat([rgb[:, None], source_rgb.view(-1, V, 3)], dim=-2) * att[..., None], dim=-2))
+        return torch.cat(rgbs, 0)
+
+    def reconstruct(self, feats, images, masks, calibs, bbox, mesh_param, smpl=None, scan=None, persps=None):
+        """The reference's signature -> (verts float64 [Nv,3], faces int32 [T,3], rgbs float32 [Nv,3]) as numpy.  An empty hull or a volume
+        that never crosses the threshold gives three empty arrays (scikit-image would raise); masks, calibs and persps are cut to
+        num_views.  The grid spans 0 .. 512 along x and z whatever loadSize is, as in the reference."""
+        if persps is None:
+            raise NotImplementedError('projection: only the perspective projection is built')
+        from . import gnr_recon as R
+        with torch.no_grad():
+            V, N = self.num_views, self.N_grid
+            top, bottom = float(bbox[0]), float(bbox[1])
+            bb_min = [0 - self.width / 2, top - self.height / 2, 0 - self.width / 2]
+            bb_max = [512 - self.width / 2, bottom - self.height / 2, 512 - self.width / 2]
+            calibs, persps, masks = calibs[:V].contiguous(), persps[:V].contiguous(), masks[:V]
+            center = mesh_param['center'].to(calibs.device)
+            kwargs = {'feats': feats, 'images': images, 'smpl': smpl, 'calibs': calibs, 'mesh_param': mesh_param, 'persps': persps}
+            vol = self.octree_reconstruct(None, masks, grid=(bb_min, bb_max), **kwargs)
+            if sum(self.recon_levels) == 0:
+                return R.empty_mesh()
+            verts_idx, faces, normals = R.marching_cubes(vol, self.threshold)
+            if verts_idx.shape[0] == 0 or faces.shape[0] == 0:
+                return R.empty_mesh()
+            verts, pts = R.to_world(verts_idx, N, (top, bottom), mesh_param['spatial_freq'], center)
+            if self.opt.get('laplacian', 0) > 0:
+                verts = R.laplacian_smooth(verts, faces, int(self.opt.laplacian))
+                pts = verts.float()
+            rgbs = self._vertex_colours(pts, normals, feats, images, calibs, persps, smpl, mesh_param)
+            return verts.cpu().numpy(), faces.cpu().numpy(), rgbs.float().cpu().numpy()

@@ -2384,3 +2384,160 @@ def hg_conv_block(x, weights, norms, out=None, groups=32, eps=1e-5):
         _lib.check(lib.xr_hg_conv_block(xp, ldx, N, H, W, Cin, Cout, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(wd), *[_ptr(t) for t in norms], groups, float(eps),
                                         yp, ldy, C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()), 'xr_hg_conv_block')
     return out
+
+
+# ---------------------------------------------------------------- GNR mesh reconstruction (csrc/xr_gnr_recon.hip)
+GNR_RECON_MAX_N = 1024          # XR_GNR_RECON_MAX_N
+
+
+def gnr_recon_kernels_available():
+    """the loaded library handle has xr_gnr_recon.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_gnr_recon_hull')
+
+
+def gnr_recon_grid(N, bb_min, bb_max, spatial_freq, center, coords=None):
+    """the grid's description for the entry points below: np.linspace(bb_min[a], bb_max[a], N) per axis as (start, stop, step) host
+    doubles, spatial_freq, center [3] (device fp32); or `coords` [N^3,3] (device fp32), the caller's own points"""
+    lin = (C.c_double * 9)()
+    for a in range(3):
+        lin[3 * a], lin[3 * a + 1] = float(bb_min[a]), float(bb_max[a])
+        lin[3 * a + 2] = (float(bb_max[a]) - float(bb_min[a])) / (N - 1)
+    if coords is not None:
+        coords = _f32c(coords).reshape(-1, 3)
+        if coords.shape[0] != N ** 3:
+            raise _lib.XrError('gnr_recon_grid: coords must hold N^3 points')
+    return {'N': int(N), 'lin': lin, 'sf': float(spatial_freq), 'center': _f32c(center).reshape(3), 'coords': coords}
+
+
+def _gc_grid_args(grid):
+    return (grid['lin'], grid['sf'], _ptr(grid['center']), _ptr(grid['coords']))
+
+
+def _gc_views(w2c, cams):
+    w2c, cams = _f32c(w2c).reshape(-1, 4, 4), _f32c(cams)
+    return w2c, cams, (_ptr(w2c), _ptr(cams), cams.shape[-1], w2c.shape[0])
+
+
+def gnr_recon_hull(grid, w2c, cams, masks, width, height):
+    """-> state [N,N,N] uint8 (1 = inside the hull and below the last index of every axis)"""
+    N, dev = grid['N'], grid['center'].device
+    w2c, cams, views = _gc_views(w2c, cams)
+    masks = _f32c(masks).reshape(w2c.shape[0], masks.shape[-2], masks.shape[-1])
+    state = torch.empty((N, N, N), dtype=torch.uint8, device=dev)
+    with _span('xr_gnr_recon_hull', N ** 3):
+        _lib.check(_lib.load().xr_gnr_recon_hull(N, *_gc_grid_args(grid), *views, _ptr(masks), masks.shape[-2], masks.shape[-1], float(width),
+                                                 float(height), _ptr(state), _stream()), 'xr_gnr_recon_hull')
+    return state
+
+
+def gnr_recon_select(grid, reso, state, w2c, cams, width, height):
+    """the level's test set in C order -> (flat [M] int32, pts [M,3], xy [M,V,2]).  ONE blocking read (M)."""
+    N, dev = grid['N'], state.device
+    lib = _lib.load()
+    w2c, cams, views = _gc_views(w2c, cams)
+    nbytes = int(lib.xr_gnr_recon_select_workspace_bytes(N, int(reso)))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int32, device=dev)
+    with _span('xr_gnr_recon_select_count', N ** 3 // reso ** 3):
+        _lib.check(lib.xr_gnr_recon_select_count(N, int(reso), _ptr(state), _ptr(ws), ws.numel() * 4, _ptr(total), _stream()), 'xr_gnr_recon_select_count')
+    M = int(total.item())
+    if M < 0:
+        raise _lib.XrError('gnr_recon_select: more than 2^31 - 1 points')
+    V = w2c.shape[0]
+    flat = torch.empty((M,), dtype=torch.int32, device=dev)
+    pts = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    xy = torch.empty((M, V, 2), dtype=torch.float32, device=dev)
+    if M > 0:
+        with _span('xr_gnr_recon_select_write', N ** 3 // reso ** 3):
+            _lib.check(lib.xr_gnr_recon_select_write(N, int(reso), *_gc_grid_args(grid), *views, float(width), float(height), _ptr(state), _ptr(ws), M,
+                                                     _ptr(flat), _ptr(pts), _ptr(xy), _stream()), 'xr_gnr_recon_select_write')
+    return flat, pts, xy
+
+
+def gnr_recon_scatter(flat, values, volume, state, gamma=None):
+    """volume[flat] = values (sigmoid(gamma values) with a gamma), state[flat] = 0, in place"""
+    M, N = flat.shape[0], volume.shape[0]
+    values = _f32c(values).reshape(-1)
+    if values.shape[0] != M:
+        raise _lib.XrError('gnr_recon_scatter: one value per selected point')
+    with _span('xr_gnr_recon_scatter', M):
+        _lib.check(_lib.load().xr_gnr_recon_scatter(_ptr(_i32c(flat)), _ptr(values), M, int(gamma is not None), float(gamma or 0.0), N, _ptr(volume),
+                                                    _ptr(state), _stream()), 'xr_gnr_recon_scatter')
+
+
+def gnr_recon_fold(reso, volume, state):
+    """the skip-and-fill step after a level with reso >= 2, in place"""
+    N = volume.shape[0]
+    lib = _lib.load()
+    nbytes = int(lib.xr_gnr_recon_fold_workspace_bytes(N, int(reso)))
+    ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=volume.device)
+    with _span('xr_gnr_recon_fold', N ** 3):
+        _lib.check(lib.xr_gnr_recon_fold(N, int(reso), _ptr(volume), _ptr(state), _ptr(ws), ws.numel() * 4, _stream()), 'xr_gnr_recon_fold')
+
+
+def gnr_recon_surface(volume, level):
+    """iso-surface with welded vertices -> (verts_idx [Nv,3] fp32, faces [T,3] int32, normals [Nv,3] fp32).  ONE blocking read (Nv, T)."""
+    volume = _f32c(volume)
+    N, dev = volume.shape[0], volume.device
+    lib = _lib.load()
+    nbytes = int(lib.xr_gnr_recon_surface_workspace_bytes(N))
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    totals = torch.empty((2,), dtype=torch.int32, device=dev)
+    with _span('xr_gnr_recon_surface_count', N ** 3):
+        _lib.check(lib.xr_gnr_recon_surface_count(_ptr(volume), N, float(level), _ptr(ws), ws.numel() * 4, _ptr(totals), _stream()), 'xr_gnr_recon_surface_count')
+    Nv, T = (int(v) for v in totals.tolist())
+    if Nv < 0 or T < 0:
+        raise _lib.XrError('gnr_recon_surface: more than 2^31 - 1 vertices or triangles')
+    verts = torch.empty((Nv, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((Nv, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    if Nv > 0:
+        with _span('xr_gnr_recon_surface_write', N ** 3):
+            _lib.check(lib.xr_gnr_recon_surface_write(_ptr(volume), N, float(level), _ptr(ws), Nv, T, _ptr(verts), _ptr(normals), _ptr(faces), _stream()),
+                       'xr_gnr_recon_surface_write')
+    return verts, faces, normals
+
+
+def gnr_recon_world(verts_idx, N, extent, spatial_freq, center):
+    """index coordinates -> (verts [Nv,3] float64 in the reference's world coordinates, pts = their fp32 rounding)"""
+    verts_idx = _f32c(verts_idx).reshape(-1, 3)
+    Nv, dev = verts_idx.shape[0], verts_idx.device
+    verts = torch.empty((Nv, 3), dtype=torch.float64, device=dev)
+    pts = torch.empty((Nv, 3), dtype=torch.float32, device=dev)
+    ext = (C.c_double * 3)(*[float(e) for e in extent])
+    center = _f32c(center).reshape(3)
+    with _span('xr_gnr_recon_world', Nv):
+        _lib.check(_lib.load().xr_gnr_recon_world(_ptr(verts_idx), Nv, int(N), ext, float(spatial_freq), _ptr(center), _ptr(verts), _ptr(pts), _stream()),
+                   'xr_gnr_recon_world')
+    return verts, pts
+
+
+def gnr_recon_point_rows(pts, dirs, w2c, cams, width, height, cam_c, rot=None):
+    """-> (xy [n,V,2], attdirs [n,V+1,3]) of the points with the query directions `dirs`"""
+    pts, dirs = _f32c(pts).reshape(-1, 3), _f32c(dirs).reshape(-1, 3)
+    n, dev = pts.shape[0], pts.device
+    w2c, cams, views = _gc_views(w2c, cams)
+    V = w2c.shape[0]
+    cam_c = _f32c(cam_c).reshape(V, 3)
+    r9 = _f32c(rot).reshape(9) if rot is not None else None
+    xy = torch.empty((n, V, 2), dtype=torch.float32, device=dev)
+    attdirs = torch.empty((n, V + 1, 3), dtype=torch.float32, device=dev)
+    with _span('xr_gnr_recon_point_rows', n):
+        _lib.check(_lib.load().xr_gnr_recon_point_rows(_ptr(pts), _ptr(dirs), n, *views, float(width), float(height), _ptr(cam_c), _ptr(r9), _ptr(xy),
+                                                       _ptr(attdirs), _stream()), 'xr_gnr_recon_point_rows')
+    return xy, attdirs
+
+
+def gnr_recon_smooth(verts, faces, rowptr, cols, iterations, lamb=0.5):
+    """Laplacian filter with the volume constraint on float64 vertices -> a new [Nv,3] tensor"""
+    if verts.dtype != torch.float64:
+        raise _lib.XrError('gnr_recon_smooth takes float64 vertices')
+    out = verts.contiguous().clone()
+    Nv, T = out.shape[0], faces.shape[0]
+    lib = _lib.load()
+    nbytes = int(lib.xr_gnr_recon_smooth_workspace_bytes(Nv, T))
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=out.device)
+    with _span('xr_gnr_recon_smooth', Nv * max(int(iterations), 0)):
+        _lib.check(lib.xr_gnr_recon_smooth(_ptr(out), Nv, _ptr(_i32c(faces)), T, _ptr(_i32c(rowptr)), _ptr(_i32c(cols)), cols.shape[0], int(iterations),
+                                           float(lamb), _ptr(ws), ws.numel() * 8, _stream()), 'xr_gnr_recon_smooth')
+    return out
