@@ -69,6 +69,10 @@ def test_hull_with_the_training_draws(edev, gold):
     _T().check_hull(edev, gold, 48, 4, 'trn')
 
 
+def test_hull_of_288_rays_scans_the_counts_in_two_sweeps(edev, gold):
+    _T().check_hull(edev, gold, 48, 2, tile=6)
+
+
 def test_hull_nan_ray_camera_behind_and_nothing_to_do(edev, gold):
     _T().check_hull_edges(edev, gold)
 

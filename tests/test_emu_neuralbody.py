@@ -55,6 +55,10 @@ def test_structure_matches_the_restatement_exactly(edev, V, out_sh):
     _T().check_structure(edev, V, out_sh)
 
 
+def test_structure_with_two_scan_sweeps_matches_the_restatement_exactly(edev):
+    _T().check_structure(edev, *_T().STRUCT_TWO_SWEEPS)
+
+
 def test_bad_out_sh_and_volume_over_the_cap_launch_nothing(edev):
     _T().check_structure_errors(edev)
 

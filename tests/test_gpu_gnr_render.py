@@ -79,9 +79,11 @@ def bits(t):
     return np.ascontiguousarray(t.detach().cpu().numpy()).view(np.int32)
 
 
-def hull_inputs(dev, gold, mode, R, V):
+def hull_inputs(dev, gold, mode, R, V, tile=1):
+    """the scene's first R rays, repeated `tile` times (the scan of the rays' counts takes 256 per sweep: 6 x 48 rays reach its second)"""
     sc = scene()
-    return dict(rays=sc['rays'][:R].to(dev), t_vals=torch.from_numpy(gold[mode + '.t_vals'][:R]).to(dev), calibs=sc['calibs'][:V].to(dev),
+    return dict(rays=sc['rays'][:R].repeat(tile, 1).to(dev), t_vals=torch.from_numpy(gold[mode + '.t_vals'][:R]).repeat(tile, 1).to(dev),
+                calibs=sc['calibs'][:V].to(dev),
                 persps=sc['persps'][:V].to(dev), masks=sc['masks'][:V].to(dev), width=sc['width'], height=sc['width'],
                 depth=sc['smpl']['depth'][:V].to(dev), rot=sc['smpl']['rot'][0].to(dev))
 
@@ -99,9 +101,10 @@ def hull32(inp):
 
 
 # ------------------------------------------------------------------------------------------ hull
-def check_hull(dev, gold, R, V, mode='inf'):
+def check_hull(dev, gold, R, V, mode='inf', tile=1):
     from xrnerf_amd import gnr_render as GR
-    inp = hull_inputs(dev, gold, mode, R, V)
+    inp = hull_inputs(dev, gold, mode, R, V, tile)
+    R *= tile
     S = inp['t_vals'].shape[1]
     got = GR.visual_hull(**inp)
     sync()
@@ -147,7 +150,7 @@ def check_hull(dev, gold, R, V, mode='inf'):
     sure = margin > 1e-4
     print('  smpl_vis: %d differ among %d compared (bar 0), %d left out (bar %.2f), true for %.2f' % (
         int((vis != vis_want)[sure].sum()), int(sure.sum()), int((~sure).sum()), 0.01 * sure.size, float(vis.mean()) if vis.size else 0.0))
-    if R == 48:                                                    # (the smaller cases are prefixes of this one)
+    if R >= 48:                                                    # (the smaller cases are prefixes of this one)
         assert (~sure).sum() <= 0.01 * sure.size
     assert np.array_equal(vis[sure], vis_want[sure])
     again = GR.visual_hull(**inp)
@@ -603,6 +606,11 @@ def test_hull_flags_order_and_rows(dev, gold, R, V):
 @pytest.mark.gpu
 def test_hull_with_the_training_draws(dev, gold):
     check_hull(dev, gold, 48, 4, 'trn')
+
+
+@pytest.mark.gpu
+def test_hull_of_288_rays_scans_the_counts_in_two_sweeps(dev, gold):
+    check_hull(dev, gold, 48, 2, tile=6)
 
 
 @pytest.mark.gpu

@@ -28,6 +28,8 @@ G = os.path.join(ROOT, 'tests', 'golden')
 
 STRUCT_V = (1, 63, 65, 257)
 STRUCT_SH = ((32, 32, 32), (32, 64, 32), (64, 32, 96))
+# 1 179 648 cells = 288 count workgroups: the scan of their counts takes 256 per sweep, so the far-corner voxel's workgroup gets a carry
+STRUCT_TWO_SWEEPS = (257, (96, 128, 96))
 # every (Cin, Cout, strided) of the network
 CONV_LAYERS = ((16, 16, False), (32, 32, False), (64, 64, False), (128, 128, False), (16, 32, True), (32, 64, True), (64, 128, True),
                (128, 128, True))
@@ -523,6 +525,11 @@ def check_state_dict_and_registry(gold):
 @pytest.mark.parametrize('V', STRUCT_V)
 def test_structure_matches_the_restatement_exactly(dev, V, out_sh):
     check_structure(dev, V, out_sh)
+
+
+@pytest.mark.gpu
+def test_structure_with_two_scan_sweeps_matches_the_restatement_exactly(dev):
+    check_structure(dev, *STRUCT_TWO_SWEEPS)
 
 
 @pytest.mark.gpu

@@ -5,7 +5,7 @@
 //                        workgroups share a CU); every lane reads the SAME tile entry (an LDS broadcast), keeps the smallest
 //                        d2 = (dx dx + dy dy) + dz dz and its index; ascending order + strict `<` = lowest index on a tie
 //   k_ani_select_*       pind = flags | argmin(dist) and nonzero(pind): per-workgroup counts and minima, ONE workgroup that finds the
-//                        global minimum and scans the counts, then the ranked write (ballot + popcount).  Three launches, no
+//                        global minimum and scans the counts, then the ranked write (the scans: xr_scan.h).  Three launches, no
 //                        workgroup waits for another
 //   k_ani_blend_fwd/bwd  thread = point: softmax over 24 channels of log(smpl_bw[idx] + 1e-9) + logits, the gathered row never stored
 //   k_ani_skin_fwd/bwd   thread = point: the 2 x 24 matrices (top three rows) in LDS, read as broadcasts; blend, invert by adjugate /
@@ -15,10 +15,11 @@
 // Compiled with -ffp-contract=off: every expression is fp32 in the written order (the fp32 torch restatement of the query matches it
 // bit for bit).
 #include "xr_common.h"
-#include "xr_wave.h"
+#include "xr_scan.h"
 #include "../../include/xrnerf_mi355_aninerf.h"
 
 #define AN_BLOCK 256
+static_assert(AN_BLOCK == XR_SCAN_BLOCK, "the shared workgroup routines are written for 256 threads");
 #define AN_WAVES (AN_BLOCK / 64)
 #define AN_J XR_ANI_JOINTS
 #define AN_TILE XR_ANI_CLOSEST_TILE
@@ -128,9 +129,8 @@ __global__ void __launch_bounds__(AN_BLOCK) k_ani_select_order(const int32_t* __
                                                                int32_t* __restrict__ count) {
     __shared__ float s_d[AN_BLOCK];
     __shared__ uint32_t s_i[AN_BLOCK];
-    __shared__ uint32_t s_w[AN_WAVES];
     __shared__ uint32_t s_forced;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const uint32_t t = threadIdx.x;
     float d = __uint_as_float(0x7f800000u);
     uint32_t bi = 0xffffffffu;
     for (uint32_t b = t; b < nb; b += AN_BLOCK)
@@ -146,36 +146,18 @@ __global__ void __launch_bounds__(AN_BLOCK) k_ani_select_order(const int32_t* __
     __syncthreads();
     const uint32_t forced = s_forced;
     const uint32_t extra_block = (forced != 0xffffffffu && flags[forced] == 0) ? forced / AN_BLOCK : 0xffffffffu;
-    // exclusive scan of the counts, 256 workgroups per sweep
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nb; b0 += AN_BLOCK) {
-        const uint32_t b = b0 + t;
-        const uint32_t c = b < nb ? ws.cnt[b] + (b == extra_block ? 1u : 0u) : 0u;
-        const uint32_t incl = xr_wave_incl_sum(c);
-        __syncthreads();                                           // s_w of the previous sweep has been read
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < AN_WAVES; ++w) { if (w < wave) before += s_w[w]; total += s_w[w]; }
-        if (b < nb) ws.off[b] = carry + before + incl - c;
-        carry += total;
-    }
-    if (t == 0) count[0] = (int32_t)carry;
+    const uint64_t total = xr_scan_sweeps(nb, [&](uint32_t b) { return ws.cnt[b] + (b == extra_block ? 1u : 0u); },
+                                          [&](uint32_t b, uint32_t base) { ws.off[b] = base; });
+    if (t == 0) count[0] = xr_scan_total(total);
 }
 
 __global__ void __launch_bounds__(AN_BLOCK) k_ani_select_write(const int32_t* __restrict__ flags, uint32_t n, AnSelWs ws,
                                                                int32_t* __restrict__ list) {
-    __shared__ uint32_t s_w[AN_WAVES];
-    const uint32_t i = blockIdx.x * AN_BLOCK + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * AN_BLOCK + threadIdx.x;
     const bool sel = i < n && (flags[i] != 0 || i == ws.forced[0]);
-    const unsigned long long m = __ballot(sel);
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (!sel) return;
-    uint32_t rank = ws.off[blockIdx.x];
-    for (uint32_t w = 0; w < wave; ++w) rank += s_w[w];
-    rank += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    list[rank] = (int32_t)i;
+    uint32_t sum;
+    const uint32_t rank = xr_block_excl_flag(sel, &sum);
+    if (sel) list[ws.off[blockIdx.x] + rank] = (int32_t)i;
 }
 
 // ------------------------------------------------------------------------------------------ blend-weight head

@@ -4,8 +4,8 @@
 //                  its projection into every source view by the hull's own device functions (xr_gnr_project.h) and the nearest sample
 //                  of the dilated masks -> one state byte: 1 = still to be evaluated, 0 = processed
 //   k_gc_sel_count / scan / k_gc_sel_write   a level's test set -- indices multiples of reso, state 1 -- compacted in C order:
-//                  per-workgroup counts, a two-level exclusive scan (k_gc_scan_part, k_gc_scan, k_gc_scan_add), ranked write of (flat,
-//                  point, normalised projections)
+//                  per-workgroup counts, a two-level exclusive scan (xr_scan.h's xr_scan_two_level), ranked write of (flat, point,
+//                  normalised projections)
 //   k_gc_scatter   the level's occupancies into the fp32 volume at `flat`, the state byte cleared
 //   k_gc_cells / k_gc_fill   the fold: per coarse cell min, max, the centre's state -> skip decision (in double) and fill value; then
 //                  per fine point the lexicographically LAST skipped cell among the (up to 8) cells whose closed block covers it
@@ -18,13 +18,14 @@
 //                  order, the signed volume as a fixed-order sum, the rescale about the origin
 // No floating-point atomics and no atomic cursor anywhere: the same input gives the same bits.
 #include "xr_common.h"
-#include "xr_wave.h"
+#define XR_SCAN_TWO_LEVEL
+#include "xr_scan.h"
 #include "../../include/xrnerf_mi355_gnr.h"
 #include "../../include/xrnerf_mi355_gnr_recon.h"
 #include "xr_gnr_project.h"
 
 #define GC_BLOCK 256
-#define GC_WAVES (GC_BLOCK / 64)
+static_assert(GC_BLOCK == XR_SCAN_BLOCK, "the shared workgroup routines are written for 256 threads");
 #define GC_MAX_N XR_GNR_RECON_MAX_N
 
 struct GcGrid {
@@ -55,57 +56,6 @@ static __device__ inline bool gc_in_hull(const GrHull& a, const float* p) {
     return true;
 }
 
-// exclusive prefix of c over the workgroup's threads and the workgroup's sum; EVERY thread of the workgroup calls it
-static __device__ inline uint32_t gc_block_excl(uint32_t c, uint32_t* sum) {
-    __shared__ uint32_t s_w[GC_WAVES];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t incl = xr_wave_incl_sum(c);
-    __syncthreads();                                               // s_w of an earlier call has been read
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < GC_WAVES; ++w) { if (w < wave) before += s_w[w]; all += s_w[w]; }
-    *sum = all;
-    return before + incl - c;
-}
-
-// one workgroup: counts [n] become exclusive bases in place, their sum goes to total[0] (k_gr_scan's pattern).  The sum is carried in
-// 64 bits: one that does not fit int32 is reported as -1 (the bases are then meaningless and the caller must not use them)
-__global__ void __launch_bounds__(GC_BLOCK) k_gc_scan(uint32_t n, uint32_t* __restrict__ counts, int32_t* __restrict__ total) {
-    uint64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n; b0 += GC_BLOCK) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t c = b < n ? counts[b] : 0u;
-        uint32_t sum;
-        const uint32_t ex = gc_block_excl(c, &sum);
-        if (b < n) counts[b] = (uint32_t)carry + ex;
-        carry += sum;
-    }
-    if (threadIdx.x == 0) total[0] = carry > 0x7fffffffull ? -1 : (int32_t)carry;
-}
-
-// the scan of n counts in two levels: every workgroup scans its 256 counts and leaves their sum, k_gc_scan scans the sums (n / 256 of
-// them: 2059 at 513^3 grid points), every workgroup adds its base.  sums: xr_div_up(n, GC_BLOCK) words behind the counts
-__global__ void __launch_bounds__(GC_BLOCK) k_gc_scan_part(uint32_t n, uint32_t* __restrict__ counts, uint32_t* __restrict__ sums) {
-    const uint32_t b = blockIdx.x * GC_BLOCK + threadIdx.x;
-    uint32_t sum;
-    const uint32_t ex = gc_block_excl(b < n ? counts[b] : 0u, &sum);
-    if (b < n) counts[b] = ex;
-    if (threadIdx.x == 0) sums[blockIdx.x] = sum;
-}
-
-__global__ void __launch_bounds__(GC_BLOCK) k_gc_scan_add(uint32_t n, uint32_t* __restrict__ counts, const uint32_t* __restrict__ sums) {
-    const uint32_t b = blockIdx.x * GC_BLOCK + threadIdx.x;
-    if (b < n) counts[b] += sums[blockIdx.x];
-}
-
-static void gc_scan(hipStream_t st, uint32_t n, uint32_t* counts, uint32_t* sums, int32_t* total) {
-    const uint32_t n2 = xr_div_up(n, GC_BLOCK);
-    hipLaunchKernelGGL(k_gc_scan_part, dim3(n2), dim3(GC_BLOCK), 0, st, n, counts, sums);
-    hipLaunchKernelGGL(k_gc_scan, dim3(1), dim3(GC_BLOCK), 0, st, n2, sums, total);
-    hipLaunchKernelGGL(k_gc_scan_add, dim3(n2), dim3(GC_BLOCK), 0, st, n, counts, (const uint32_t*)sums);
-}
-
 // ------------------------------------------------------------------------------------------ grid hull
 __global__ void __launch_bounds__(GC_BLOCK) k_gc_hull(GcGrid g, GrHull a, uint8_t* __restrict__ state) {
     const uint64_t id = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x, N = g.N;
@@ -132,7 +82,7 @@ __global__ void __launch_bounds__(GC_BLOCK) k_gc_sel_count(GcLevel l, const uint
     uint32_t ijk[3], sum;
     uint64_t flat;
     const bool on = gc_lattice(l, (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x, ijk, &flat) && state[flat] == 1;
-    gc_block_excl(on ? 1u : 0u, &sum);
+    xr_block_excl_flag(on, &sum);
     if (threadIdx.x == 0) bcount[blockIdx.x] = sum;
 }
 
@@ -142,7 +92,7 @@ __global__ void __launch_bounds__(GC_BLOCK) k_gc_sel_write(GcLevel l, GcGrid g, 
     uint32_t ijk[3], sum;
     uint64_t flat;
     const bool on = gc_lattice(l, (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x, ijk, &flat) && state[flat] == 1;
-    const uint64_t m = (uint64_t)bbase[blockIdx.x] + gc_block_excl(on ? 1u : 0u, &sum);
+    const uint64_t m = (uint64_t)bbase[blockIdx.x] + xr_block_excl_flag(on, &sum);
     if (!on || m >= M) return;                                     // (M is the scan's total: the second test never holds)
     float p[3];
     gc_point(g, ijk, flat, p);
@@ -516,7 +466,7 @@ __global__ void __launch_bounds__(GC_BLOCK) k_mc_count(McVol m, uint32_t* __rest
         nt = mc_triangles(mc_case(m, id, ijk));
     }
     uint32_t sum;
-    const uint32_t ex = gc_block_excl(nv | (nt << 16), &sum);      // at most 3 and 5 per thread: both fit 16 bits over 256 threads
+    const uint32_t ex = xr_block_excl(nv | (nt << 16), &sum);      // at most 3 and 5 per thread: both fit 16 bits over 256 threads
     if (id < total) rank[id] = ex & 0xffffu;
     if (threadIdx.x == 0) { bsum_v[blockIdx.x] = sum & 0xffffu; bsum_t[blockIdx.x] = sum >> 16; }
 }
@@ -569,7 +519,7 @@ __global__ void __launch_bounds__(GC_BLOCK) k_mc_tris(McVol m, const uint32_t* _
     if (id < total) { mc_ijk(m, id, ijk); k = mc_case(m, id, ijk); }
     const uint32_t nt = mc_triangles(k);
     uint32_t sum;
-    uint64_t tri = (uint64_t)gc_block_excl(nt, &sum);
+    uint64_t tri = (uint64_t)xr_block_excl(nt, &sum);
     if (nt == 0) return;
     tri += bbase_t[blockIdx.x];
     for (uint32_t t = 0; t < nt; ++t, ++tri) {
@@ -737,7 +687,7 @@ extern "C" int xr_gnr_recon_select_count(uint32_t N, uint32_t reso, const uint8_
     if (workspace_bytes < xr_gnr_recon_select_workspace_bytes(N, reso)) { xr_set_error("%s: workspace too small", __func__); return XR_ENOMEM; }
     const uint32_t nb = xr_div_up((uint64_t)l.L * l.L * l.L, GC_BLOCK);
     hipLaunchKernelGGL(k_gc_sel_count, dim3(nb), dim3(GC_BLOCK), 0, (hipStream_t)stream, l, state, (uint32_t*)workspace);
-    gc_scan((hipStream_t)stream, nb, (uint32_t*)workspace, (uint32_t*)workspace + nb, total);
+    xr_scan_two_level((hipStream_t)stream, nb, (uint32_t*)workspace, (uint32_t*)workspace + nb, total);
     XR_LAUNCH_CHECK();
     return 0;
 }
@@ -815,8 +765,8 @@ extern "C" int xr_gnr_recon_surface_count(const float* volume, uint32_t N, float
     m.N = N; m.vol = volume; m.level = level;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mc_count, dim3(nb), dim3(GC_BLOCK), 0, st, m, rank, bv, bt);
-    gc_scan(st, nb, bv, bt + nb, totals2);
-    gc_scan(st, nb, bt, bt + nb + xr_div_up(nb, GC_BLOCK), totals2 + 1);
+    xr_scan_two_level(st, nb, bv, bt + nb, totals2);
+    xr_scan_two_level(st, nb, bt, bt + nb + xr_div_up(nb, GC_BLOCK), totals2 + 1);
     XR_LAUNCH_CHECK();
     return 0;
 }

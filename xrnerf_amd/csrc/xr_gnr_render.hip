@@ -6,12 +6,13 @@
 //   k_gr_flag      thread = (ray, sample): the sample point, its projection into every source view (w2c, division by clamp(z, 1e-9),
 //                  five-coefficient distortion, intrinsics, normalisation) and the nearest mask sample of torch's grid_sample
 //   k_gr_ray       thread = ray: the ray's flags become ranks inside the ray, their number the ray's count
-//   k_gr_scan      one workgroup: exclusive scan of the counts -> (count, base) per ray and the total
+//   k_gr_scan      one workgroup: exclusive scan of the counts -> (count, base) per ray and the total (xr_scan.h)
 //   k_gr_write     thread = (ray, sample): a survivor writes its row at base + rank -- ascending flat index, the order of
 //                  torch.nonzero -- with what the later stages need, so nothing is projected a second time
 //   k_gr_gather    thread = (survivor, view, float4 of channels): bilinear samples of the channel-last feature maps and of the
 //                  images, written at a row stride into the network's input
-//   k_gr_gather_bwd  the same walk, adding w g to the feature maps in 64-bit fixed point (k_gr_absmax, k_gr_scale, k_gr_gather_cvt around it)
+//   k_gr_gather_bwd  the same walk, adding w g to the feature maps in 64-bit fixed point (xr_fixed.h; k_gr_absmax and k_gr_gather_cvt
+//                  around it)
 //   k_gr_comp_fwd  wave = ray, lane = survivor, 64 at a time in sample order (outside the hull the reference's -1e4 gives alpha = 0
 //                  and a factor of exactly 1.0f, so leaving those samples out changes no factor of the running product); the
 //                  transmittance is a product scan over the lanes, the sums a butterfly: a fixed order, the same bits every run
@@ -19,10 +20,13 @@
 //                  transmittance, no atomics
 #include "xr_common.h"
 #include "xr_wave.h"
+#include "xr_scan.h"
+#include "xr_fixed.h"
 #include "../../include/xrnerf_mi355_gnr.h"
 #include "xr_gnr_project.h"
 
 #define GR_BLOCK 256
+static_assert(GR_BLOCK == XR_SCAN_BLOCK && GR_BLOCK == XR_FIX_BLOCK, "the shared workgroup routines are written for 256 threads");
 #define GR_WAVES (GR_BLOCK / 64)
 #define GR_V XR_GNR_MAX_VIEWS
 
@@ -62,24 +66,11 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_ray(uint32_t R, uint32_t S, int
     table[2ull * r] = n;
 }
 
-// exclusive scan of table[r][0] -> table[r][1], the total -> total[0]; one workgroup, 256 rays per sweep (k_nb_scan's pattern)
+// exclusive scan of table[r][0] -> table[r][1], the total -> total[0]; one workgroup
 __global__ void __launch_bounds__(GR_BLOCK) k_gr_scan(uint32_t R, int32_t* __restrict__ table, int32_t* __restrict__ total) {
-    __shared__ uint32_t s_w[GR_WAVES];
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < R; b0 += GR_BLOCK) {
-        const uint32_t b = b0 + t;
-        const uint32_t c = b < R ? (uint32_t)table[2ull * b] : 0u;
-        const uint32_t incl = xr_wave_incl_sum(c);
-        __syncthreads();                                           // s_w of the previous sweep has been read
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, sum = 0;
-        for (uint32_t w = 0; w < GR_WAVES; ++w) { if (w < wave) before += s_w[w]; sum += s_w[w]; }
-        if (b < R) table[2ull * b + 1] = (int32_t)(carry + before + incl - c);
-        carry += sum;
-    }
-    if (t == 0) total[0] = (int32_t)carry;
+    const uint64_t sum = xr_scan_sweeps(R, [&](uint32_t b) { return (uint32_t)table[2ull * b]; },
+                                        [&](uint32_t b, uint32_t base) { table[2ull * b + 1] = (int32_t)base; });
+    if (threadIdx.x == 0) total[0] = xr_scan_total(sum);
 }
 
 struct GrRows {
@@ -253,11 +244,8 @@ extern "C" int xr_gnr_gather(const float* xy, uint32_t M, uint32_t V, const floa
     return 0;
 }
 
-// ---- backward: the gradient in the feature maps, 64-bit fixed point (k_nb_sample_bwd's scheme: integer adds commute, so two runs
-// give the same bits)
-#define GR_MAX_BMAX 1024u
-#define GR_BWD_HEAD (GR_MAX_BMAX * sizeof(float) + sizeof(double))
-
+// ---- backward: the gradient in the feature maps, 64-bit fixed point (xr_fixed.h: integer adds commute, so two runs give the same
+// bits).  The scale's n is M: a map element receives at most one corner of every (point, view) of its view
 struct GrGatherBwd {
     const float* xy; uint32_t M, V;
     const float* grad; uint32_t ld, col0;                // row (m V + v) of grad, columns col0 .. col0 + C
@@ -266,7 +254,6 @@ struct GrGatherBwd {
 };
 
 __global__ void __launch_bounds__(GR_BLOCK) k_gr_absmax(GrGatherBwd a, float* __restrict__ bmax) {
-    __shared__ float s_m[GR_BLOCK];
     float m = 0.f;
     const uint64_t total = (uint64_t)a.M * a.V * a.C;
     for (uint64_t e = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x; e < total; e += (uint64_t)gridDim.x * GR_BLOCK) {
@@ -274,29 +261,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_absmax(GrGatherBwd a, float* __
         const float g = fabsf(a.grad[mv * a.ld + a.col0 + (uint32_t)(e - mv * a.C)]);
         if (g <= 3.0e38f) m = fmaxf(m, g);                          // (a NaN or an infinite entry contributes nothing, here either)
     }
-    s_m[threadIdx.x] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < GR_BLOCK; ++k) m = fmaxf(m, s_m[k]);
-        bmax[blockIdx.x] = m;
-    }
-}
-
-// 2^(61 - b - e) with max |grad| < 2^e and M <= 2^b: a map element receives at most one corner of every (point, view) of its view, each
-// |w g| <= |g|, so its sum stays below 2^61 in magnitude.  ONE workgroup folds the block maxima into the scale, once per call
-__global__ void __launch_bounds__(GR_BLOCK) k_gr_scale(const float* __restrict__ bmax, uint32_t n_bmax, uint32_t n, double* __restrict__ scale) {
-    __shared__ float s_m[GR_BLOCK];
-    float m = 0.f;
-    for (uint32_t e = threadIdx.x; e < n_bmax; e += GR_BLOCK) m = fmaxf(m, bmax[e]);
-    s_m[threadIdx.x] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < GR_BLOCK; ++k) m = fmaxf(m, s_m[k]);
-        int ex = 0, b = 0;
-        if (m > 0.f) frexpf(m, &ex);
-        while (b < 31 && (1u << b) < n) ++b;
-        scale[0] = ldexp(1.0, 61 - b - ex);
-    }
+    xr_fix_block_max(m, bmax);
 }
 
 __global__ void __launch_bounds__(GR_BLOCK) k_gr_gather_bwd(GrGatherBwd a) {
@@ -317,11 +282,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_gather_bwd(GrGatherBwd a) {
         unsigned long long* d = a.acc + (((uint64_t)v * a.fh + y) * a.fw + x) * a.C + 4ull * q;
         const double w = (double)c.w[k];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double t = (w * (double)ge[j]) * scale;
-            // (a NaN or an infinite gradient contributes nothing: |t| < 2^61 for every finite one, and llrint is undefined beyond 2^63)
-            if (t != 0.0 && fabs(t) < 4.0e18) atomicAdd(d + j, (unsigned long long)(long long)llrint(t));
-        }
+        for (int j = 0; j < 4; ++j) xr_fix_add(d + j, w, ge[j], scale);
     }
 }
 
@@ -329,12 +290,12 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_gather_cvt(const double* __rest
                                                             uint64_t n, float* __restrict__ out) {
     const uint64_t e = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
     if (e >= n) return;
-    out[e] = (float)((double)(long long)acc[e] / scale[0]);
+    out[e] = xr_fix_to_float(acc[e], scale[0]);
 }
 
 extern "C" size_t xr_gnr_gather_backward_workspace_bytes(uint32_t V, int fh, int fw, uint32_t C) {
     if (fh < 1 || fw < 1) return 0;
-    return (size_t)(GR_BWD_HEAD + (uint64_t)V * (uint32_t)fh * (uint32_t)fw * C * sizeof(unsigned long long));
+    return (size_t)(XR_FIX_HEAD + (uint64_t)V * (uint32_t)fh * (uint32_t)fw * C * sizeof(unsigned long long));
 }
 
 extern "C" int xr_gnr_gather_backward(const float* xy, uint32_t M, uint32_t V, const float* grad, uint32_t ld, uint32_t col0, int fh, int fw,
@@ -348,23 +309,21 @@ extern "C" int xr_gnr_gather_backward(const float* xy, uint32_t M, uint32_t V, c
     if (workspace_bytes < xr_gnr_gather_backward_workspace_bytes(V, fh, fw, C)) { xr_set_error("%s: workspace too small", __func__); return XR_ENOMEM; }
     const uint64_t el = (uint64_t)V * (uint32_t)fh * (uint32_t)fw * C;
     hipStream_t st = (hipStream_t)stream;
-    float* bmax = (float*)workspace;
-    double* scale = (double*)((char*)workspace + GR_MAX_BMAX * sizeof(float));
-    unsigned long long* acc = (unsigned long long*)((char*)workspace + GR_BWD_HEAD);
-    XR_HIP(hipMemsetAsync(workspace, 0, GR_BWD_HEAD + (size_t)el * sizeof(unsigned long long), st));
+    const XrFixWs ws = xr_fix_ws(workspace);
+    XR_HIP(hipMemsetAsync(workspace, 0, XR_FIX_HEAD + (size_t)el * sizeof(unsigned long long), st));
     GrGatherBwd a;
-    a.xy = xy; a.M = M; a.V = V; a.grad = grad; a.ld = ld; a.col0 = col0; a.fh = fh; a.fw = fw; a.C = C; a.scale = scale; a.acc = acc;
+    a.xy = xy; a.M = M; a.V = V; a.grad = grad; a.ld = ld; a.col0 = col0; a.fh = fh; a.fw = fw; a.C = C; a.scale = ws.scale; a.acc = ws.acc;
     uint32_t nbm = 1;
     if (M != 0) {
         XR_REQUIRE(xy && grad, "null pointer");
         XR_REQUIRE((uint64_t)col0 + C <= ld, "the row stride is smaller than the row");
         nbm = xr_div_up((uint64_t)M * V * C, GR_BLOCK);
-        if (nbm > GR_MAX_BMAX) nbm = GR_MAX_BMAX;
-        hipLaunchKernelGGL(k_gr_absmax, dim3(nbm), dim3(GR_BLOCK), 0, st, a, bmax);
+        if (nbm > XR_FIX_MAX_BMAX) nbm = XR_FIX_MAX_BMAX;
+        hipLaunchKernelGGL(k_gr_absmax, dim3(nbm), dim3(GR_BLOCK), 0, st, a, ws.bmax);
     }
-    hipLaunchKernelGGL(k_gr_scale, dim3(1), dim3(GR_BLOCK), 0, st, (const float*)bmax, nbm, M, scale);
+    hipLaunchKernelGGL(k_xr_fix_scale, dim3(1), dim3(XR_FIX_BLOCK), 0, st, (const float*)ws.bmax, nbm, M, ws.scale);
     if (M != 0) hipLaunchKernelGGL(k_gr_gather_bwd, dim3(xr_div_up((uint64_t)M * V * (C / 4), GR_BLOCK)), dim3(GR_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_gr_gather_cvt, dim3(xr_div_up(el, GR_BLOCK)), dim3(GR_BLOCK), 0, st, (const double*)scale, (const unsigned long long*)acc, el, d_feats);
+    hipLaunchKernelGGL(k_gr_gather_cvt, dim3(xr_div_up(el, GR_BLOCK)), dim3(GR_BLOCK), 0, st, (const double*)ws.scale, (const unsigned long long*)ws.acc, el, d_feats);
     XR_LAUNCH_CHECK();
     return 0;
 }

@@ -1,8 +1,8 @@
 // NeuralBody (configs/neuralbody/nb_zjumocap_*.py) for gfx950: what `spconv` and the dense feature volumes are to the reference.
 //   k_nb_mark0 / k_nb_mark_down   mark the active cells of a level in its index volume (level 0: the vertices' voxels; level l + 1: the
 //                                 up to eight output cells every input row feeds).  All marks store the same value: no atomics
-//   k_nb_count / _scan / _rank    count / scan / ranked write over the cells (the pattern of xr_ani_select): rows in ascending linear
-//                                 index, the index volume rewritten in place to the row of every cell
+//   k_nb_count / _scan / _rank    count / scan / ranked write over the cells (xr_scan.h): rows in ascending linear index, the index
+//                                 volume rewritten in place to the row of every cell
 //   k_nb_subm_table, k_nb_down_tables   [N, 27] neighbour tables, one (row, tap) per thread
 //   k_nb_conv       workgroup = 64 output rows.  Per tap that some row of the tile has (one ballot each), the gathered input rows
 //                   (zero where -1) and W[k] pass through LDS in slices of 32 input channels to v_mfma_f32_32x32x2_f32: a wave owns
@@ -12,21 +12,21 @@
 //                   k_nb_fold sums the slabs in chunk order
 //   k_nb_sample_fwd thread = (point, float4 of channels): the pose transform and the normalisation, then the eight corners of the
 //                   thread's level through its index volume, torch's grid_sample arithmetic and corner order
-//   k_nb_sample_bwd the same walk, adding w g to the rows in 64-bit fixed point (integer adds commute: repeatable bits)
+//   k_nb_sample_bwd the same walk, adding w g to the rows in 64-bit fixed point (xr_fixed.h: integer adds commute, repeatable bits)
 // Compiled with -ffp-contract=off: every expression is fp32 in the written order.
 #include "xr_common.h"
-#include "xr_wave.h"
+#include "xr_scan.h"
+#include "xr_fixed.h"
 #include "../../include/xrnerf_mi355_neuralbody.h"
 
 #define NB_BLOCK 256
-#define NB_WAVES (NB_BLOCK / 64)
+static_assert(NB_BLOCK == XR_SCAN_BLOCK && NB_BLOCK == XR_FIX_BLOCK, "the shared workgroup routines are written for 256 threads");
 #define NB_SPAN 16                              // cells per thread of the count / rank kernels
 #define NB_CELLS_PER_BLOCK (NB_BLOCK * NB_SPAN)
 #define NB_TAPS XR_NB_TAPS
 #define NB_TILE XR_NB_TILE
 #define NB_KC 32                                // input channels per LDS slice of the convolution
 #define NB_MARK (-2)
-#define NB_MAX_BMAX 1024u
 
 typedef float nb_f32x16 __attribute__((ext_vector_type(16)));
 #define NB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -104,61 +104,35 @@ __global__ void __launch_bounds__(NB_BLOCK) k_nb_mark_down(const int32_t* __rest
 
 // ------------------------------------------------------------------------------------------ structure: count / scan / rank
 __global__ void __launch_bounds__(NB_BLOCK) k_nb_count(const int32_t* __restrict__ vol, uint32_t cells, uint32_t* __restrict__ cnt) {
-    __shared__ uint32_t s_c[NB_WAVES];
-    const uint32_t base = blockIdx.x * NB_CELLS_PER_BLOCK, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t c = 0;
+    const uint32_t base = blockIdx.x * NB_CELLS_PER_BLOCK;
+    uint32_t c = 0, sum;
     for (uint32_t s = 0; s < NB_SPAN; ++s) {
         const uint32_t cell = base + s * NB_BLOCK + threadIdx.x;
         if (cell < cells && vol[cell] == NB_MARK) ++c;
     }
-    c = xr_wave_sum(c);
-    if (lane == 0) s_c[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < NB_WAVES; ++w) t += s_c[w];
-        cnt[blockIdx.x] = t;
-    }
+    xr_block_excl(c, &sum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = sum;
 }
 
-// exclusive scan of cnt [nb] -> off [nb], the total -> count[0]; one workgroup, 256 entries per sweep
+// exclusive scan of cnt [nb] -> off [nb], the total -> count[0]; one workgroup
 __global__ void __launch_bounds__(NB_BLOCK) k_nb_scan(const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t* __restrict__ off,
                                                       int32_t* __restrict__ count) {
-    __shared__ uint32_t s_w[NB_WAVES];
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nb; b0 += NB_BLOCK) {
-        const uint32_t b = b0 + t;
-        const uint32_t c = b < nb ? cnt[b] : 0u;
-        const uint32_t incl = xr_wave_incl_sum(c);
-        __syncthreads();                                           // s_w of the previous sweep has been read
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < NB_WAVES; ++w) { if (w < wave) before += s_w[w]; total += s_w[w]; }
-        if (b < nb) off[b] = carry + before + incl - c;
-        carry += total;
-    }
-    if (t == 0) count[0] = (int32_t)carry;
+    const uint64_t total = xr_scan_sweeps(nb, [&](uint32_t b) { return cnt[b]; }, [&](uint32_t b, uint32_t base) { off[b] = base; });
+    if (threadIdx.x == 0) count[0] = xr_scan_total(total);
 }
 
 __global__ void __launch_bounds__(NB_BLOCK) k_nb_rank(int32_t* __restrict__ vol, uint32_t cells, const uint32_t* __restrict__ cnt,
                                                       const uint32_t* __restrict__ off, int32_t* __restrict__ rows, uint32_t cap) {
-    __shared__ uint32_t s_w[NB_WAVES];
     if (cnt[blockIdx.x] == 0) return;                              // (the whole workgroup: nothing marked here, the cells stay -1)
-    const uint32_t base = blockIdx.x * NB_CELLS_PER_BLOCK, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t base = blockIdx.x * NB_CELLS_PER_BLOCK;
     uint32_t running = off[blockIdx.x];
     for (uint32_t s = 0; s < NB_SPAN; ++s) {
         const uint32_t cell = base + s * NB_BLOCK + threadIdx.x;
         const bool f = cell < cells && vol[cell] == NB_MARK;
-        const unsigned long long m = __ballot(f);
-        __syncthreads();                                           // s_w of the previous span has been read
-        if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < NB_WAVES; ++w) { if (w < wave) before += s_w[w]; total += s_w[w]; }
+        uint32_t total;
+        const uint32_t before = xr_block_excl_flag(f, &total);
         if (f) {
-            const uint32_t rank = running + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t rank = running + before;
             vol[cell] = (int32_t)rank;
             if (rank < cap) rows[rank] = (int32_t)cell;
         }
@@ -631,7 +605,6 @@ struct NbSampleBwd {
 };
 
 __global__ void __launch_bounds__(NB_BLOCK) k_nb_absmax(const float* __restrict__ grad, uint32_t ld, uint32_t n, float* __restrict__ bmax) {
-    __shared__ float s_m[NB_BLOCK];
     float m = 0.f;
     const uint64_t total = (uint64_t)n * NB_Q4;
     for (uint64_t e = (uint64_t)blockIdx.x * NB_BLOCK + threadIdx.x; e < total; e += (uint64_t)gridDim.x * NB_BLOCK) {
@@ -639,30 +612,7 @@ __global__ void __launch_bounds__(NB_BLOCK) k_nb_absmax(const float* __restrict_
         const float4 v = *reinterpret_cast<const float4*>(grad + (uint64_t)i * ld + 4u * q);
         m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
     }
-    s_m[threadIdx.x] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < NB_BLOCK; ++k) m = fmaxf(m, s_m[k]);
-        bmax[blockIdx.x] = m;
-    }
-}
-
-// 2^(61 - b - e) with max |grad| < 2^e and n <= 2^b: the sum of a row element's contributions stays below 2^61 in magnitude.
-// ONE workgroup folds the block maxima into the scale, once per call; the scatter and the convert kernel read that scalar
-__global__ void __launch_bounds__(NB_BLOCK) k_nb_scale(const float* __restrict__ bmax, uint32_t n_bmax, uint32_t n, double* __restrict__ scale) {
-    __shared__ float s_m[NB_BLOCK];
-    float m = 0.f;
-    for (uint32_t e = threadIdx.x; e < n_bmax; e += NB_BLOCK) m = fmaxf(m, bmax[e]);
-    s_m[threadIdx.x] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < NB_BLOCK; ++k) m = fmaxf(m, s_m[k]);
-        if (!(m < 3.0e38f)) m = 3.0e38f;
-        int ex = 0, b = 0;
-        if (m > 0.f) frexpf(m, &ex);
-        while (b < 31 && (1u << b) < n) ++b;
-        scale[0] = ldexp(1.0, 61 - b - ex);
-    }
+    xr_fix_block_max(m, bmax);
 }
 
 __global__ void __launch_bounds__(NB_BLOCK) k_nb_sample_bwd(NbSampleBwd a) {
@@ -683,11 +633,7 @@ __global__ void __launch_bounds__(NB_BLOCK) k_nb_sample_bwd(NbSampleBwd a) {
         unsigned long long* d = acc + (uint64_t)(uint32_t)cn.row[c] * C + 4u * c4;
         const double w = (double)cn.w[c];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double v = (w * (double)ge[k]) * scale;
-            // (a NaN or an infinite gradient contributes nothing: |v| < 2^61 for every finite one, and llrint is undefined beyond 2^63)
-            if (v != 0.0 && fabs(v) < 4.0e18) atomicAdd(d + k, (unsigned long long)(long long)llrint(v));
-        }
+        for (int k = 0; k < 4; ++k) xr_fix_add(d + k, w, ge[k], scale);
     }
 }
 
@@ -699,18 +645,16 @@ __global__ void __launch_bounds__(NB_BLOCK) k_nb_sample_cvt(NbSampleCvt a) {
     const double scale = a.scale[0];
     const int l = e < a.end[0] ? 0 : (e < a.end[1] ? 1 : (e < a.end[2] ? 2 : 3));
     const uint64_t first = l == 0 ? 0ull : a.end[l - 1];
-    a.out[l][e - first] = (float)((double)(long long)a.acc[e] / scale);
+    a.out[l][e - first] = xr_fix_to_float(a.acc[e], scale);
 }
 
 static inline int nb_level_channels(int l) { return l == 0 ? 32 : (l == 1 ? 64 : 128); }
-// workspace: block maxima [NB_MAX_BMAX] floats | the scale (one double) | the 64-bit accumulators
-#define NB_BWD_HEAD (NB_MAX_BMAX * sizeof(float) + sizeof(double))
 
 extern "C" size_t xr_nb_sample_backward_workspace_bytes(const uint32_t* n_rows) {
     if (!n_rows) return 0;
     uint64_t el = 0;
     for (int l = 0; l < 4; ++l) el += (uint64_t)n_rows[l] * nb_level_channels(l);
-    return (size_t)(NB_BWD_HEAD + el * sizeof(unsigned long long));
+    return (size_t)(XR_FIX_HEAD + el * sizeof(unsigned long long));
 }
 
 extern "C" int xr_nb_sample_backward(const float* pts, const float* R, const float* T, const float* min_xyz, float voxel, int D, int H,
@@ -731,25 +675,23 @@ extern "C" int xr_nb_sample_backward(const float* pts, const float* R, const flo
     XR_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 7u) == 0, "the workspace must be 8-byte aligned");
     if (workspace_bytes < xr_nb_sample_backward_workspace_bytes(n_rows)) { xr_set_error("%s: workspace too small", __func__); return XR_ENOMEM; }
     hipStream_t st = (hipStream_t)stream;
-    float* bmax = (float*)workspace;
-    double* scale = (double*)((char*)workspace + NB_MAX_BMAX * sizeof(float));
-    unsigned long long* acc = (unsigned long long*)((char*)workspace + NB_BWD_HEAD);
-    XR_HIP(hipMemsetAsync(workspace, 0, NB_BWD_HEAD + (size_t)el * sizeof(unsigned long long), st));
+    const XrFixWs ws = xr_fix_ws(workspace);
+    XR_HIP(hipMemsetAsync(workspace, 0, XR_FIX_HEAD + (size_t)el * sizeof(unsigned long long), st));
     uint32_t nbm = 1;
     if (n != 0) {
         XR_REQUIRE(grad != nullptr && nb_aligned16(grad) && ld >= XR_NB_FEATURES && (ld & 3u) == 0,
                    "grad must be 16-byte aligned with a row stride >= 352 that is a multiple of 4");
         nbm = xr_div_up((uint64_t)n * NB_Q4, NB_BLOCK);
-        if (nbm > NB_MAX_BMAX) nbm = NB_MAX_BMAX;
-        hipLaunchKernelGGL(k_nb_absmax, dim3(nbm), dim3(NB_BLOCK), 0, st, grad, ld, n, bmax);
-        hipLaunchKernelGGL(k_nb_scale, dim3(1), dim3(NB_BLOCK), 0, st, (const float*)bmax, nbm, n, scale);
-        a.grad = grad; a.ld = ld; a.scale = scale;
-        for (int l = 0; l < 4; ++l) a.acc[l] = acc + (l == 0 ? 0ull : end[l - 1]);
+        if (nbm > XR_FIX_MAX_BMAX) nbm = XR_FIX_MAX_BMAX;
+        hipLaunchKernelGGL(k_nb_absmax, dim3(nbm), dim3(NB_BLOCK), 0, st, grad, ld, n, ws.bmax);
+        hipLaunchKernelGGL(k_xr_fix_scale, dim3(1), dim3(XR_FIX_BLOCK), 0, st, (const float*)ws.bmax, nbm, n, ws.scale);
+        a.grad = grad; a.ld = ld; a.scale = ws.scale;
+        for (int l = 0; l < 4; ++l) a.acc[l] = ws.acc + (l == 0 ? 0ull : end[l - 1]);
         hipLaunchKernelGGL(k_nb_sample_bwd, dim3(xr_div_up((uint64_t)n * NB_Q4, NB_BLOCK)), dim3(NB_BLOCK), 0, st, a);
     }
     NbSampleCvt c;
-    if (n == 0) hipLaunchKernelGGL(k_nb_scale, dim3(1), dim3(NB_BLOCK), 0, st, (const float*)bmax, nbm, n, scale);
-    c.scale = scale; c.acc = acc;
+    if (n == 0) hipLaunchKernelGGL(k_xr_fix_scale, dim3(1), dim3(XR_FIX_BLOCK), 0, st, (const float*)ws.bmax, nbm, n, ws.scale);
+    c.scale = ws.scale; c.acc = ws.acc;
     for (int l = 0; l < 4; ++l) { c.end[l] = end[l]; c.out[l] = (float*)grad_feats[l]; }
     hipLaunchKernelGGL(k_nb_sample_cvt, dim3(xr_div_up(el, NB_BLOCK)), dim3(NB_BLOCK), 0, st, c);
     XR_LAUNCH_CHECK();

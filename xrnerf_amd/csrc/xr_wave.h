@@ -1,6 +1,6 @@
-// wave64 collectives of the wave-per-ray kernels and of the count / scan / rank kernels (xr_render.h, xr_mip.hip, xr_bungee.hip,
-// xr_vanilla.hip, xr_kilo.hip, xr_gnr_render.hip, xr_aninerf.hip, xr_neuralbody.hip): the ONE copy of the few lines the renderers'
-// determinism rests on.  Every scan is a Hillis-Steele sweep over the offsets 1, 2, 4, .. 32 and every sum a butterfly over
+// wave64 collectives of the wave-per-ray kernels (xr_render.h, xr_mip.hip, xr_bungee.hip, xr_vanilla.hip, xr_kilo.hip,
+// xr_gnr_render.hip) and of the workgroup scans of the count / scan / rank kernels (xr_scan.h, under xr_neuralbody.hip, xr_aninerf.hip,
+// xr_gnr_render.hip and xr_gnr_recon.hip): the ONE copy of the few lines the renderers' determinism rests on.  Every scan is a Hillis-Steele sweep over the offsets 1, 2, 4, .. 32 and every sum a butterfly over
 // 32, 16, .. 1, so the order of the additions / products is fixed by the lane number alone: the same input gives the same bits on every
 // launch.  Each computes in the type of its argument: double restates torch's CPU cumsum / cumprod of fp32 values, which accumulate in
 // double; float is GNR's compositor; uint32_t the counts of the scan kernels.
