@@ -264,6 +264,12 @@ GNR_ENCODER_SIGNATURES = {
     'xr_hg_conv_block': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _u32] + [_vp] * 12 + [_u32, _f, _vp, _u32, _vp, _sz, _vp]),
 }
 
+# GNR body depth maps (csrc/xr_gnr_raster.hip, declared in include/xrnerf_mi355_gnr_raster.h): a table of its own as well
+GNR_RASTER_SIGNATURES = {
+    'xr_gnr_raster_workspace_bytes': (_sz, [_u32, _u32, _u32, _u32]),
+    'xr_gnr_raster_forward': (_i32, [_vp, _u32, _u32, _vp, _u32, _u32, _u32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -321,7 +327,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
-            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()):
+            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -54,6 +54,9 @@ SOURCES = {
     # GNR mesh reconstruction (grid hull, octree bookkeeping, iso-surface, Laplacian filter): a grid point is (i step + start) / f + c in
     # double, rounded once, and must equal numpy's bit for bit -- no fused multiply-add; the projection is the hull's
     'xr_gnr_recon.hip': ['-ffp-contract=off'],
+    # GNR body depth maps (z-buffer rasteriser, vertex visibility): inside / outside is a comparison of A0 u + A3 v + A6 with -eps and the
+    # stored coefficients and depths equal the reference's host build bit for bit -- no fused multiply-add
+    'xr_gnr_raster.hip': ['-ffp-contract=off'],
     # GNR image encoder (hourglass convolutions on the fp32 MFMA, GroupNorm statistics, pool, bicubic upsampling): the only index
     # decision on a float is the bicubic tap, the floor of ONE product (scale * dst), which contraction cannot change: contraction stays on
     'xr_gnr_encoder.hip': [],

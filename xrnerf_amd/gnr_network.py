@@ -115,7 +115,17 @@ class GnrNetwork(BaseNerfNetwork):
                 smpl['t_verts'] = data['smpl_t_verts'][0].to(device=dev)
                 smpl['t_faces'] = data['smpl_t_faces'][0].to(device=dev)
             if opt.use_smpl_depth:
-                smpl['depth'] = data['smpl_depth'][0].to(device=dev)[:, None, ...]
+                given = data.get('smpl_depth')
+                if given is not None and len(given) > 0 and given[0].numel() > 0:
+                    smpl['depth'] = given[0].to(device=dev)[:, None, ...]
+                else:
+                    # a frame without depth files (a re-posed body, a user's capture): the maps are rasterised from the body itself
+                    from .gnr_raster import depth_maps
+                    if opt.projection_mode != 'perspective':
+                        raise NotImplementedError('projection: only the perspective projection is built')
+                    r = self.nerf_renderer
+                    smpl['depth'] = depth_maps(smpl['verts'], smpl['faces'], data['calib'][0].to(device=dev)[:self.num_views],
+                                               data['persps'][0].to(device=dev)[:self.num_views], r.height, r.width)
         scan = [data['scan_verts'][0].to(device=dev), data['scan_faces'][0].to(device=dev)] if 'scan_verts' in data.keys() else None
         return {'images': data['img'][0].to(device=dev), 'calibs': data['calib'][0].to(device=dev),
                 'bbox': list(data['bbox'][0].cpu().numpy().astype(np.int32)), 'masks': data['mask'][0].to(device=dev),

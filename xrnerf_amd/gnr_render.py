@@ -245,12 +245,16 @@ def _project64(verts, w2c, cam):
     return np.stack([cam[0] * x + cam[2], cam[1] * y + cam[3]], 1), p[:, 2]
 
 
-def synthetic_scene(seed=0, R=48, S=16, V=4, size=64, C=16, fh=12, fw=20, subdivisions=3, distance=3.0, dilate=5):
+def synthetic_scene(seed=0, R=48, S=16, V=4, size=64, C=16, fh=12, fw=20, subdivisions=3, distance=3.0, dilate=5, depth='dilated'):
     """the generated inputs of one render_rays call, float32 host tensors: a synthetic_mesh body; V source cameras on a ring at
     `distance` looking at the body's centre and one query camera, 11-entry camera rows (fx, fy, cx, cy, k1, k2, p1, p2, k3, near,
     far) with non-zero distortion; masks and smpl['depth'] = the projected vertices dilated by `dilate` pixels; images [V,3,size,size];
     feature maps [V,C,fh,fw]; R rays (start, end) through random pixels of the query view's central three quarters; ground-truth colours; the
-    training draws t_rand and noise"""
+    training draws t_rand and noise.  depth='raster': smpl['depth'] = the body's real depth maps (gnr_raster.depth_maps) instead of the
+    dilated stand-in"""
+    if depth not in ('dilated', 'raster'):
+        raise ValueError("depth is 'dilated' or 'raster'")
+    kind = depth
     from .gnr import synthetic_mesh
     rng = np.random.default_rng([seed, 77])
     mesh = synthetic_mesh(subdivisions, seed)
@@ -295,6 +299,9 @@ def synthetic_scene(seed=0, R=48, S=16, V=4, size=64, C=16, fh=12, fw=20, subdiv
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
     smpl = dict(mesh)
     smpl['depth'] = depth
+    if kind == 'raster':
+        from .gnr_raster import depth_maps
+        smpl['depth'] = depth_maps(mesh['verts'], mesh['faces'], f32(np.stack([c[0] for c in cams])), f32(np.stack([c[1] for c in cams])), size, size)
     return {'smpl': smpl, 'calibs': f32(np.stack([c[0] for c in cams])), 'persps': f32(np.stack([c[1] for c in cams])),
             'q_calib': f32(q_calib), 'q_persps': f32(q_persp), 'masks': masks, 'images': f32(rng.uniform(0, 1, (V, 3, size, size))),
             'feats': f32(rng.normal(0, 1, (V, C, fh, fw))), 'rays': f32(rays), 'rgb_gt': f32(rng.uniform(0, 1, (R, 3))),
@@ -597,6 +604,15 @@ class GnrRenderer:
         smpl_vis = vis(smpl['depth']) if self.use_occlusion else None
         scan_vis = vis(smpl['scan_depth']) if self.use_occlusion_net and 'scan_depth' in smpl else None
         return inside, smpl_vis, scan_vis
+
+    def scan_depth_maps(self, scan, calibs, persps):
+        """scan = [verts [N,3], faces [F,3]] -> the scan's depth maps [V,1,height,width] in the source views (gnr_raster.depth_maps).
+        Nothing calls it by itself: a caller that puts the result into smpl['scan_depth'] switches the occlusion head's supervision
+        (occ_gt = scan_vis) on, a loss existing runs do not have."""
+        from .gnr_raster import depth_maps
+        if persps is None:
+            raise NotImplementedError('projection: only the perspective projection is built')
+        return depth_maps(scan[0], scan[1], calibs[:self.num_views], persps[:self.num_views], self.height, self.width)
 
     def make_nerf_input(self, pts, feats, images, smpl, calibs, mesh_param, persps=None, is_train=True):
         """the reference's layout [N, V, 3 + 7 + C + 3] and source_rgb [N, V, 3] (render_rays builds the network's rows directly instead)"""

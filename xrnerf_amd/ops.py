@@ -2541,3 +2541,50 @@ def gnr_recon_smooth(verts, faces, rowptr, cols, iterations, lamb=0.5):
         _lib.check(lib.xr_gnr_recon_smooth(_ptr(out), Nv, _ptr(_i32c(faces)), T, _ptr(_i32c(rowptr)), _ptr(_i32c(cols)), cols.shape[0], int(iterations),
                                            float(lamb), _ptr(ws), ws.numel() * 8, _stream()), 'xr_gnr_recon_smooth')
     return out
+
+
+# ---------------------------------------------------------------- GNR body depth maps (csrc/xr_gnr_raster.hip)
+GNR_RASTER_MAX_SIDE = 32768     # XR_GNR_RASTER_MAX_SIDE
+
+
+def gnr_raster_kernels_available():
+    """the loaded library handle has xr_gnr_raster.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_gnr_raster_forward')
+
+
+def gnr_raster_workspace_bytes(V, N, H, W):
+    """bytes of workspace one gnr_raster_forward call needs; 0 for sizes it refuses"""
+    if min(V, N, H, W) < 0 or max(V, N, H, W) > 0xffffffff:
+        return 0
+    return int(_lib.load().xr_gnr_raster_workspace_bytes(int(V), int(N), int(H), int(W)))
+
+
+def gnr_raster_forward(verts, faces, H, W, persp, double_face=False, eps=1e-6, out=None):
+    """the z-buffer rasteriser over V views of one mesh: verts [V,N,3] fp32 as the reference's render_forward takes them (x and y
+    are divided by z in the kernel with `persp`), faces [F,3] int32 -> (index [V,H,W] int64, -1 where empty; coeff [V,H,W,3];
+    visual [V,N] bool; depth [V,H,W], 0 where empty).  `out`: the four tensors to write into (contiguous; slices of larger buffers
+    along the first axis are)."""
+    verts, faces = _f32c(verts), _i32c(faces)
+    if verts.dim() != 3 or verts.shape[-1] != 3 or faces.dim() != 2 or faces.shape[-1] != 3:
+        raise _lib.XrError('gnr_raster_forward: verts [V,N,3], faces [F,3]')
+    V, N, F = verts.shape[0], verts.shape[1], faces.shape[0]
+    H, W = int(H), int(W)
+    lib = _lib.load()
+    nbytes = gnr_raster_workspace_bytes(V, N, H, W) if min(H, W) >= 0 and F <= 0xffffffff else 0
+    if nbytes == 0 or not float(eps) >= 0.0:
+        raise _lib.XrError('gnr_raster_forward: refused (eps >= 0; 1 <= H, W <= %d; V H W and V N within int32; F < 2^32 - 1): V %d N %d F %d H %d W %d eps %r'
+                           % (GNR_RASTER_MAX_SIDE, V, N, F, H, W, eps))
+    dev = verts.device
+    shapes = ((V, H, W), (V, H, W, 3), (V, N), (V, H, W))
+    dtypes = (torch.int64, torch.float32, torch.bool, torch.float32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    if len(out) != 4 or any(tuple(t.shape) != s or t.dtype != d for t, s, d in zip(out, shapes, dtypes)):
+        raise _lib.XrError('gnr_raster_forward: out = (index int64 [V,H,W], coeff fp32 [V,H,W,3], visual bool [V,N], depth fp32 [V,H,W])')
+    ws = _ws(dev, nbytes + 8, 'gnr_raster')
+    off = (-ws.data_ptr()) % 8
+    with _span('xr_gnr_raster_forward', V * F):
+        _lib.check(lib.xr_gnr_raster_forward(_ptr(verts), V, N, _ptr(faces), F, H, W, int(bool(persp)), int(bool(double_face)), float(eps),
+                                             *[_ptr(t) for t in out], C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()),
+                   'xr_gnr_raster_forward')
+    return tuple(out)
