@@ -270,6 +270,14 @@ GNR_RASTER_SIGNATURES = {
     'xr_gnr_raster_forward': (_i32, [_vp, _u32, _u32, _vp, _u32, _u32, _u32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# Test-set evaluation (csrc/xr_eval.hip, declared in include/xrnerf_mi355_eval.h): a table of its own as well
+_i64 = C.c_int64
+EVAL_SIGNATURES = {
+    'xr_eval_workspace_bytes': (_sz, [_u32, _u32, _u32, _u32]),
+    'xr_eval_ssim': (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _i64, _i64, _i64, _i64, _vp, _u32, _d, _d, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'xr_eval_to8b_pair': (_i32, [_vp, _vp, _u32, _u32, _u32, _i64, _i64, _i64, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -327,7 +335,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
-            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()):
+            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

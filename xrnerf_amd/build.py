@@ -60,6 +60,9 @@ SOURCES = {
     # GNR image encoder (hourglass convolutions on the fp32 MFMA, GroupNorm statistics, pool, bicubic upsampling): the only index
     # decision on a float is the bicubic tap, the floor of ONE product (scale * dst), which contraction cannot change: contraction stays on
     'xr_gnr_encoder.hip': [],
+    # test-set evaluation (windowed moments, SSIM map, squared error, 8-bit image): double arithmetic whose bits the host build of the
+    # same source (tests/hip_emu) reproduces -- no fused multiply-add
+    'xr_eval.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

@@ -2588,3 +2588,81 @@ def gnr_raster_forward(verts, faces, H, W, persp, double_face=False, eps=1e-6, o
                                              *[_ptr(t) for t in out], C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()),
                    'xr_gnr_raster_forward')
     return tuple(out)
+
+
+# ---------------------------------------------------------------- test-set evaluation (csrc/xr_eval.hip)
+EVAL_MAX_RADIUS = 5             # XR_EVAL_MAX_RADIUS
+EVAL_MAX_CHANNELS = 4           # XR_EVAL_MAX_CHANNELS
+
+
+def eval_kernels_available():
+    """the loaded library handle has xr_eval.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_eval_ssim')
+
+
+def eval_workspace_bytes(B, H, W, C):
+    """bytes of workspace one eval_ssim call needs; 0 for sizes it refuses"""
+    if min(B, H, W, C) < 0 or max(B, H, W, C) > 0xffffffff:
+        return 0
+    return int(_lib.load().xr_eval_workspace_bytes(int(B), int(H), int(W), int(C)))
+
+
+def _eval_raw(t, what):
+    """the data pointer of a strided fp32 device tensor (the eval entry points take element strides, so no copy is made)"""
+    if not _on_device(t):
+        raise _lib.XrError('%s: xrnerf_amd ops need ROCm device tensors (got a %s tensor): there is no CPU fallback' % (what, t.device))
+    if t.dtype != torch.float32:
+        raise _lib.XrError('%s: fp32 images (got %s)' % (what, t.dtype))
+    return C.c_void_p(t.data_ptr())
+
+
+def eval_ssim(x, y, taps, cov_norm, C1, C2, want_map=False):
+    """x, y [B,H,W,C] fp32 device tensors of any (shared) strides -> (ssim_sum [B] double: the sum of the SSIM map S of every image,
+    sq_sum [B] double: the sum of (x - y)^2 with the difference rounded to fp32, map [B,H,W,C] double or None).  taps: the 2 r + 1
+    weights of the separable window (host floats); the arithmetic is xrnerf_mi355_eval.h's.  Nothing is read back."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise _lib.XrError('eval_ssim: x and y [B,H,W,C] of one shape (got %r, %r)' % (tuple(x.shape), tuple(y.shape)))
+    px, py = _eval_raw(x, 'eval_ssim'), _eval_raw(y, 'eval_ssim')
+    if x.stride() != y.stride():
+        x, y = x.contiguous(), y.contiguous()
+        px, py = _eval_raw(x, 'eval_ssim'), _eval_raw(y, 'eval_ssim')
+    B, H, W, Cn = (int(v) for v in x.shape)
+    taps = [float(t) for t in taps]
+    r = (len(taps) - 1) // 2
+    if len(taps) != 2 * r + 1 or r > EVAL_MAX_RADIUS:
+        raise _lib.XrError('eval_ssim: an odd number of taps, at most %d (got %d)' % (2 * EVAL_MAX_RADIUS + 1, len(taps)))
+    nbytes = eval_workspace_bytes(B, H, W, Cn)
+    if nbytes == 0 or min(H, W) < 2 * r + 1:
+        raise _lib.XrError('eval_ssim: refused (B >= 1; H, W >= 2 r + 1; 1 <= C <= %d; B H W C within int32): B %d H %d W %d C %d r %d'
+                           % (EVAL_MAX_CHANNELS, B, H, W, Cn, r))
+    dev = x.device
+    sums = torch.empty((2, B), dtype=torch.float64, device=dev)
+    smap = torch.empty((B, H, W, Cn), dtype=torch.float64, device=dev) if want_map else None
+    ws = _ws(dev, nbytes + 8, 'eval')
+    off = (-ws.data_ptr()) % 8
+    sb, sr, sp, sc = (int(s) for s in x.stride())
+    with _span('xr_eval_ssim', B * H * W * Cn, train=False):
+        _lib.check(_lib.load().xr_eval_ssim(px, py, B, H, W, Cn, sb, sr, sp, sc, (C.c_double * len(taps))(*taps), r, float(cov_norm), float(C1), float(C2),
+                                            _ptr(sums[0]), _ptr(sums[1]), _ptr(smap), C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()),
+                   'xr_eval_ssim')
+    return sums[0], sums[1], smap
+
+
+def eval_to8b_pair(rgb, gt=None):
+    """rgb (and gt) [H,W,C] fp32 device tensors -> uint8 [H, 2 W, C] = to8b(hstack(rgb, gt)), or [H,W,C] = to8b(rgb) without gt
+    (to8b: the fp32 product 255 clip(v, 0, 1), truncated; NaN -> 0)"""
+    if rgb.dim() != 3 or (gt is not None and gt.shape != rgb.shape):
+        raise _lib.XrError('eval_to8b_pair: rgb (and gt) [H,W,C] of one shape')
+    p = _eval_raw(rgb, 'eval_to8b_pair')
+    q = None if gt is None else _eval_raw(gt, 'eval_to8b_pair')
+    if gt is not None and gt.stride() != rgb.stride():
+        rgb, gt = rgb.contiguous(), gt.contiguous()
+        p, q = _eval_raw(rgb, 'eval_to8b_pair'), _eval_raw(gt, 'eval_to8b_pair')
+    H, W, Cn = (int(v) for v in rgb.shape)
+    if min(H, W) < 1 or not 1 <= Cn <= EVAL_MAX_CHANNELS or 2 * H * W * Cn > 0x7fffffff:
+        raise _lib.XrError('eval_to8b_pair: refused (H, W >= 1; 1 <= C <= %d; 2 H W C within int32): H %d W %d C %d' % (EVAL_MAX_CHANNELS, H, W, Cn))
+    out = torch.empty((H, W if gt is None else 2 * W, Cn), dtype=torch.uint8, device=rgb.device)
+    sr, sp, sc = (int(s) for s in rgb.stride())
+    with _span('xr_eval_to8b_pair', out.numel(), train=False):
+        _lib.check(_lib.load().xr_eval_to8b_pair(p, q, H, W, Cn, sr, sp, sc, _ptr(out), _stream()), 'xr_eval_to8b_pair')
+    return out
