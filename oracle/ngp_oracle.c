@@ -491,10 +491,18 @@ void xo_hashgrid_meta(int n_levels, int log2_hashmap_size, int base_resolution, 
     }
     offset[n_levels] = off;
 }
+/* The stride is 64 bits wide: a level is hashed iff its lattice has more points than its slice has entries (res^3 > hsize), at ANY
+ * resolution -- the rule of fill_meta (xrnerf_amd/csrc/xr_hashgrid.h).  A literal 32-bit reading of the published loop differs
+ * where 65536 <= res <= hsize (the loop must take its second multiply, so slices below 2^16 entries never show it): res^2 wraps to
+ * 0, the loop runs through, `hsize < stride` is false, and the level is indexed as cx + cy res with cz ignored and no hash.  A
+ * level that cannot tell z apart is useless, tcnn is not on this disk to say that it does so, and the default geometry stops at res
+ * 2048; the 64-bit rule was chosen.  GridMeta(16, 19, 16, 2.0), levels 12-15, is the geometry that tells the
+ * two apart (tests/hashgrid_geometries.py, K).  Inside the loop stride <= hsize < 2^32. */
 static inline uint32_t xo_grid_index(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t res, uint32_t hsize) {
-    uint32_t stride = 1, index = 0;
+    uint64_t stride = 1;
+    uint32_t index = 0;
     uint32_t c[3] = { cx, cy, cz };
-    for (int d = 0; d < 3 && stride <= hsize; ++d) { index += c[d] * stride; stride *= res; }
+    for (int d = 0; d < 3 && stride <= hsize; ++d) { index += c[d] * (uint32_t)stride; stride *= res; }
     if (hsize < stride) index = (cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u);
     return index % hsize;
 }

@@ -107,6 +107,9 @@ def denc_close(got, ref, arith, what=''):
 # ------------------------------------------------------------------------------------------------ table scatter
 BLOCK = 4096             # samples per binning workgroup (xr_scatter.hip S3Test::block)
 MIN_N = 16384            # rows from which the binned / run-length paths run (S3Test::min_n)
+MAX_SB = 1024            # sample blocks of a launch above which every level takes the atomic kernel (S3_MAX_SB)
+PART_ENTRIES = 8192      # table entries of one accumulate partition, the LDS capacity (S3_ENTRIES)
+MAX_PARTS = 256          # partitions of a binned level (S3_MAX_PARTS)
 RL_MAX_ENTRIES = 65536   # dense levels up to this size take the run-length kernel (S3_R_MAX_ENTRIES)
 RL_ROWS = 16             # consecutive rows a run-length thread sums in fp32 registers (S3_R_ROWS)
 RL_CHUNKS = 8            # row chunks of a run-length partition, folded in fp32 by k_scatter_fold (S3Test::rl_chunks)
@@ -134,14 +137,23 @@ def sc_test():
 
 
 def level_kinds(meta, n):
-    """per level: 'atomic' (fp32 atomics: below min_n rows), 'rl' (run-length: dense, <= 2^16 entries) or 'bin' (bin / accumulate)"""
+    """per level, the path xr_scatter.hip's s3_layout gives it at n rows: 'rl' (run-length, kind R: dense, <= 2^16 entries), 'bin'
+    (bin / accumulate: kind H, a hashed power-of-two slice of 1 .. 256 partitions of 2^13 entries at an even offset with res < 2^13, or
+    kind D, a larger dense level with 8 <= res <= 128) or 'atomic' (fp32 atomics: every level below min_n rows or above MAX_SB sample
+    blocks, and the levels no kind fits)"""
     t = sc_test()
-    min_n, rl = t['min_n'], t['rl']
+    if n < t['min_n'] or -(-n // t['block']) > MAX_SB:
+        return ['atomic'] * meta.n_levels
     out = []
     for lv in range(meta.n_levels):
-        hsize = int(meta.offset[lv + 1]) - int(meta.offset[lv])
-        dense = int(meta.resolution[lv]) ** 3 <= hsize
-        out.append('atomic' if n < min_n else 'rl' if (dense and hsize <= RL_MAX_ENTRIES and rl) else 'bin')
+        res, off = int(meta.resolution[lv]), int(meta.offset[lv])
+        hsize = int(meta.offset[lv + 1]) - off
+        hashed = res ** 3 > hsize
+        kind_h = (hashed and hsize & (hsize - 1) == 0 and hsize >= PART_ENTRIES and hsize // PART_ENTRIES <= MAX_PARTS
+                  and res < PART_ENTRIES and off % 2 == 0)
+        kind_r = not hashed and hsize <= RL_MAX_ENTRIES and bool(t['rl'])
+        kind_d = not hashed and not kind_r and 8 <= res <= 128
+        out.append('rl' if kind_r else 'bin' if (kind_h or kind_d) else 'atomic')
     return out
 
 

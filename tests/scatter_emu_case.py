@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE: one process = one setting of the scatter's test switch (XR_SC_TEST = "min_n=..,block=..,rl=..,rl_chunks=.."
 is read once per process).  Runs xr_hashgrid_bwd of the kernels' host build (tests/hip_emu) against
 oracle/ngp_oracle.c on `n` positions drawn as `mode` and prints one line per check; exit code 0 = all within tolerance.
-usage: python tests/scatter_emu_case.py <n> <rand|rays|cluster|faces>"""
+usage: python tests/scatter_emu_case.py <n> <rand|rays|cluster|faces> [n_levels,log2_hashmap_size,base_resolution,per_level_scale]
+(the level geometry, default the Lego one; per_level_scale "-" = the default scale)"""
 import os
 import sys
 
@@ -33,20 +34,33 @@ def positions(n, mode, rng):
     return x
 
 
-def main(n, mode):
+def geometry(text):
+    """"8,14,4,1.5" -> (8, 14, 4, 1.5); a scale of "-" -> None (GridMeta's default)"""
+    nl, lg, base, pls = text.split(',')
+    return int(nl), int(lg), int(base), None if pls == '-' else float(pls)
+
+
+def main(n, mode, geom=()):
     import emulib
     import oracle as O
     ok = True
     with emulib.emulated_ops():
         from xrnerf_amd import ops
-        meta, om = ops.GridMeta(), O.GridMeta()
+        meta, om = ops.GridMeta(*geom), O.GridMeta(*geom)
+        nl = meta.n_levels
+
+        def halves(k):
+            """the two launches that split the levels at k of 16 (scaled to fewer levels; one launch when there is one level)"""
+            s = k if nl >= 16 else min(max(k * nl // 16, 1), nl - 1)
+            return [lv for lv in ((s, nl), (0, s)) if lv[0] < lv[1]]
+
         rng = np.random.default_rng(n)
         x = positions(n, mode, rng)
-        dy = rng.normal(0, 1, (n, 32)).astype(np.float32)
+        dy = rng.normal(0, 1, (n, 2 * nl)).astype(np.float32)
         dy[5:9] = 0
         ref = O.hashgrid_bwd(x, dy, om)
         ld = (n + 63) // 64 * 64
-        dt = torch.zeros((32, ld))
+        dt = torch.zeros((2 * nl, ld))
         dt[:, :n] = torch.from_numpy(dy).t()
         dt = dt.contiguous()
         tx = torch.from_numpy(x)
@@ -55,7 +69,7 @@ def main(n, mode):
             nonlocal ok
             err = np.abs(g.numpy() - refv)
             tol = 2e-5 * max(1.0, float(np.abs(refv).max()))
-            bad = [lv for lv in range(16) if err[2 * int(meta.offset[lv]):2 * int(meta.offset[lv + 1])].max() > tol]
+            bad = [lv for lv in range(nl) if err[2 * int(meta.offset[lv]):2 * int(meta.offset[lv + 1])].max() > tol]
             ok = ok and not bad
             print('%-26s max err %.3e (|ref| max %.3e) levels out of tolerance: %s' % (tag, err.max(), np.abs(refv).max(), bad))
 
@@ -64,18 +78,18 @@ def main(n, mode):
             ops.hashgrid_bwd(tx, dt, meta, g, overwrite=ow)
             report('overwrite=%s' % ow, g, ref)
         g = torch.zeros(meta.n_params)
-        ops.hashgrid_bwd(tx, dt, meta, g, levels=(8, 16))
-        ops.hashgrid_bwd(tx, dt, meta, g, levels=(0, 8))
+        for lv in halves(8):
+            ops.hashgrid_bwd(tx, dt, meta, g, levels=lv)
         report('levels 8-16, then 0-8', g, ref)
         g = torch.full((meta.n_params,), 3.0)
-        ops.hashgrid_bwd(tx, dt, meta, g, levels=(3, 16), overwrite=True)
-        ops.hashgrid_bwd(tx, dt, meta, g, levels=(0, 3), overwrite=True)
+        for lv in halves(3):
+            ops.hashgrid_bwd(tx, dt, meta, g, levels=lv, overwrite=True)
         report('overwrite 3-16, then 0-3', g, ref)
         # one binned level beside three run-length levels (fewer bin workgroups per sample block than run-length levels whose maxima
         # they record: the other mapping of xr_scatter.hip's k_scatter_bin3)
         g = torch.full((meta.n_params,), 3.0)
-        ops.hashgrid_bwd(tx, dt, meta, g, levels=(0, 4), overwrite=True)
-        ops.hashgrid_bwd(tx, dt, meta, g, levels=(4, 16), overwrite=True)
+        for lv in reversed(halves(4)):
+            ops.hashgrid_bwd(tx, dt, meta, g, levels=lv, overwrite=True)
         report('overwrite 0-4, then 4-16', g, ref)
         # the fixed-point scale of the LDS sums follows the gradients' magnitude (xr_scatter.hip, S3_FIX): the same gradients times 2^-70
         g = torch.full((meta.n_params,), 3.0)
@@ -126,4 +140,4 @@ def main(n, mode):
 
 
 if __name__ == '__main__':
-    sys.exit(main(int(sys.argv[1]), sys.argv[2]))
+    sys.exit(main(int(sys.argv[1]), sys.argv[2], geometry(sys.argv[3]) if len(sys.argv) > 3 else ()))
