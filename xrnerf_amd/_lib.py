@@ -278,6 +278,12 @@ EVAL_SIGNATURES = {
     'xr_eval_to8b_pair': (_i32, [_vp, _vp, _u32, _u32, _u32, _i64, _i64, _i64, _vp, _vp]),
 }
 
+# Scene data pipelines (csrc/xr_pipeline.hip, declared in include/xrnerf_mi355_pipeline.h): a table of its own as well
+PIPELINE_SIGNATURES = {
+    'xr_pipe_ray_front': (_i32, [_vp, _f, _f, _f, _f, _u32, _u32, _vp, _u64, _u64, _vp, _u32, _vp, _i32, _i32, _i32, _f, _f, _f, _f, _f, _u32, _i32, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -335,7 +341,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
-            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+            list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
+            list(PIPELINE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

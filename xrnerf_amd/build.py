@@ -63,6 +63,9 @@ SOURCES = {
     # test-set evaluation (windowed moments, SSIM map, squared error, 8-bit image): double arithmetic whose bits the host build of the
     # same source (tests/hip_emu) reproduces -- no fused multiply-add
     'xr_eval.hip': ['-ffp-contract=off'],
+    # scene data pipelines (the fused ray front end): un-fused fp32 in the reference's operation order -- o + t d, near (1 - t) + far t,
+    # lower + (upper - lower) rand -- bit for bit the host tensor ops' results
+    'xr_pipeline.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

@@ -2666,3 +2666,82 @@ def eval_to8b_pair(rgb, gt=None):
     with _span('xr_eval_to8b_pair', out.numel(), train=False):
         _lib.check(_lib.load().xr_eval_to8b_pair(p, q, H, W, Cn, sr, sp, sc, _ptr(out), _stream()), 'xr_eval_to8b_pair')
     return out
+
+
+# ---------------------------------------------------------------- scene data pipelines (csrc/xr_pipeline.hip)
+PIPE_MAX_CHANNELS = 4           # XR_PIPE_MAX_CHANNELS
+PIPE_OUTPUTS = ('rays_o', 'rays_d', 'viewdirs', 'radii', 'near', 'far', 'z_vals', 'pts', 'target_s')
+
+
+def pipeline_kernels_available():
+    """the loaded library handle has xr_pipeline.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_pipe_ray_front')
+
+
+def pipe_ndc_factors(H, W, focal):
+    """the two factors of ndc_rays (transforms.py:37-43), evaluated in double as the reference's Python does"""
+    return -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
+
+
+def pipe_ray_front(H, W, fx, fy, cx, cy, c2w=None, sel=None, pix0=0, R=None, image=None, table=None, with_viewdirs=False, ndc=False,
+                   with_radii=False, near=0., far=1., S=0, lindisp=False, t_rand=None, want=None):
+    """the fused ray front end (xrnerf_mi355_pipeline.h) -> dict of fp32 device tensors:
+    rays_o, rays_d [R,3], viewdirs [R,3] (with_viewdirs), radii [R,1] (with_radii), near, far [R,1], z_vals [R,S] and pts [R,S,3] (S >= 1),
+    target_s [R,C] (image or table).  c2w: [3,4] device tensor; sel: [R] int32 flat pixel indices or None (R consecutive pixels from
+    pix0; R defaults to the rest of the frame); table: [R,3,3] rows (o, d, rgb).  want: the names to compute (default: all that apply);
+    the others are not computed.  Nothing is read back."""
+    H, W, S = int(H), int(W), int(S)
+    src = c2w if c2w is not None else table
+    if (c2w is None) == (table is None):
+        raise _lib.XrError('pipe_ray_front: exactly one of c2w / table')
+    if not _on_device(src) or src.dtype != torch.float32:
+        raise _lib.XrError('pipe_ray_front: xrnerf_amd ops need fp32 ROCm device tensors (got %s on %s): there is no CPU fallback' % (src.dtype, src.device))
+    dev = src.device
+    if c2w is not None:
+        if tuple(c2w.shape) != (3, 4):
+            raise _lib.XrError('pipe_ray_front: c2w [3,4] (got %r)' % (tuple(c2w.shape),))
+        if with_radii and H < 3:
+            raise ValueError('pipe_ray_front: radii need H >= 3 (below that the reference returns fewer radii than rays)')
+        if sel is not None:
+            if sel.dtype != torch.int32 or sel.dim() != 1:
+                raise _lib.XrError('pipe_ray_front: sel [R] int32')
+            n = int(sel.shape[0])
+        else:
+            n = H * W - int(pix0) if R is None else int(R)
+        if n < 0 or min(H, W) < 1 or (sel is None and int(pix0) + n > H * W) or int(pix0) < 0:
+            raise _lib.XrError('pipe_ray_front: pixels %d .. %d of a %d x %d frame' % (pix0, int(pix0) + n, H, W))
+        Cn = 0
+        if image is not None:
+            if image.dtype != torch.float32 or image.dim() != 3 or tuple(image.shape[:2]) != (H, W) or not 1 <= image.shape[2] <= PIPE_MAX_CHANNELS:
+                raise _lib.XrError('pipe_ray_front: image [H,W,C] fp32, 1 <= C <= %d (got %r %s)' % (PIPE_MAX_CHANNELS, tuple(image.shape), image.dtype))
+            Cn = int(image.shape[2])
+    else:
+        if table.dim() != 3 or tuple(table.shape[1:]) != (3, 3) or sel is not None or image is not None or with_radii:
+            raise _lib.XrError('pipe_ray_front: table [R,3,3] without sel, image or radii')
+        n, Cn = int(table.shape[0]), 3
+    if t_rand is not None and (S < 1 or t_rand.dtype != torch.float32 or tuple(t_rand.shape) != (n, S)):
+        raise _lib.XrError('pipe_ray_front: t_rand [R,S] fp32 (got %r %s at R %d S %d)' % (tuple(t_rand.shape), t_rand.dtype, n, S))
+    have = {'rays_o': (n, 3), 'rays_d': (n, 3), 'near': (n, 1), 'far': (n, 1)}
+    if with_viewdirs:
+        have['viewdirs'] = (n, 3)
+    if with_radii:
+        have['radii'] = (n, 1)
+    if S >= 1:
+        have['z_vals'], have['pts'] = (n, S), (n, S, 3)
+    if Cn:
+        have['target_s'] = (n, Cn)
+    names = [k for k in PIPE_OUTPUTS if k in have and (want is None or k in want or k in ('viewdirs', 'radii'))]
+    if want is not None and [k for k in want if k not in have]:
+        raise _lib.XrError('pipe_ray_front: %r asked for, the switches give %r' % (list(want), list(have)))
+    out = {k: torch.empty(have[k], dtype=torch.float32, device=dev) for k in names}
+    if n == 0:                  # nothing to launch (and an empty tensor has no pointer to hand over)
+        return out
+    fw, fh = pipe_ndc_factors(H, W, float(fx)) if ndc else (0., 0.)
+    cont = lambda t: None if t is None else (t if t.is_contiguous() else t.contiguous())
+    c2w, sel, image, table, t_rand = cont(c2w), cont(sel), cont(image), cont(table), cont(t_rand)
+    with _span('xr_pipe_ray_front', n * max(S, 1), train=False):
+        _lib.check(_lib.load().xr_pipe_ray_front(_ptr(c2w), float(fx), float(fy), float(cx), float(cy), H, W, _ptr(sel), int(pix0), n, _ptr(image), Cn,
+                                                _ptr(table), int(bool(with_viewdirs)), int(bool(ndc)), int(bool(with_radii)), fw, fh, 1.0, float(near),
+                                                float(far), S, int(bool(lindisp)), _ptr(t_rand), *[_ptr(out.get(k)) for k in PIPE_OUTPUTS], _stream()),
+                   'xr_pipe_ray_front')
+    return out
