@@ -284,6 +284,12 @@ PIPELINE_SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# Mip-NeRF multiscale data (csrc/xr_multiscale.hip, declared in include/xrnerf_mi355_multiscale.h): a table of its own as well
+MULTISCALE_SIGNATURES = {
+    'xr_ms_rays': (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp, _u32, _u64, _u64, _u32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xr_ms_pyramid': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -342,7 +348,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(PIPELINE_SIGNATURES.items()):
+            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

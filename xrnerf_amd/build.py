@@ -66,6 +66,9 @@ SOURCES = {
     # scene data pipelines (the fused ray front end): un-fused fp32 in the reference's operation order -- o + t d, near (1 - t) + far t,
     # lower + (upper - lower) rand -- bit for bit the host tensor ops' results
     'xr_pipeline.hip': ['-ffp-contract=off'],
+    # Mip-NeRF multiscale data (ray sampler over a camera table, box pyramid): the rays are double arithmetic in the reference's operation
+    # order, rounded to fp32 once, and the pyramid is (((a + b) + c) + d) / 4 in fp32 -- bit for bit numpy's results, nothing fused
+    'xr_multiscale.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

@@ -2745,3 +2745,102 @@ def pipe_ray_front(H, W, fx, fy, cx, cy, c2w=None, sel=None, pix0=0, R=None, ima
                                                 float(far), S, int(bool(lindisp)), _ptr(t_rand), *[_ptr(out.get(k)) for k in PIPE_OUTPUTS], _stream()),
                    'xr_pipe_ray_front')
     return out
+
+
+# ---------------------------------------------------------------- Mip-NeRF multiscale data (csrc/xr_multiscale.hip)
+MS_CAM_DOUBLES = 24             # XR_MS_CAM_DOUBLES: pix2cam (9), cam2world rows 0..2 (12), lossmult, near, far
+MS_MAX_DOWN = 8                 # XR_MS_MAX_DOWN
+MS_OUTPUTS = ('rays_o', 'rays_d', 'viewdirs', 'radii', 'lossmult', 'near', 'far', 'z_vals', 'target_s')
+
+
+def multiscale_kernels_available():
+    """the loaded library handle has xr_multiscale.hip's entry points (see gnr_kernels_available)"""
+    lib = _lib.load()
+    return hasattr(lib, 'xr_ms_rays') and hasattr(lib, 'xr_ms_pyramid')
+
+
+def ms_rays(cams, hw, prefix, sizes, images=None, idx=None, image=None, first_pixel=0, R=None, S=0, lindisp=False, t_rand=None, want=None):
+    """rays of selected pixels of a multi-camera, multi-resolution image set (xrnerf_mi355_multiscale.h) -> dict of fp32 device tensors:
+    rays_o, rays_d, viewdirs [R,3], radii, lossmult, near, far [R,1], z_vals [R,S] (S >= 1), target_s [R,3] (images given).
+    cams [n,24] double, hw [n,2] int32, prefix [n+1] int64, images [total,3] fp32: device tensors; sizes: the host's list of (H, W), the
+    same numbers as hw (nothing is read back to check a call).  Exactly one selection: idx, an int64 [R] device tensor of flat ray
+    indices (an index outside [0, total) gives a NaN ray), or image (+ first_pixel, R: default the rest of the frame).  want: the names
+    to compute (default: all that apply)."""
+    S, n = int(S), len(sizes)
+    if n < 1:
+        raise _lib.XrError('ms_rays: an empty camera table')
+    if min(int(h) for h, _ in sizes) < 3:             # dx[-2:-1] is empty below 3 rows: the reference returns fewer radii than rays
+        raise ValueError('ms_rays: every image needs H >= 3 (got %r)' % (sorted({int(h) for h, _ in sizes})[0],))
+    for t, dt, shape, name in ((cams, torch.float64, (n, MS_CAM_DOUBLES), 'cams'), (hw, torch.int32, (n, 2), 'hw'), (prefix, torch.int64, (n + 1,), 'prefix')):
+        if not isinstance(t, torch.Tensor) or not _on_device(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise _lib.XrError('ms_rays: %s must be a %s ROCm device tensor of shape %r: there is no CPU fallback' % (name, dt, shape))
+    total = sum(int(h) * int(w) for h, w in sizes)
+    dev = cams.device
+    if images is not None and (not _on_device(images) or images.dtype != torch.float32 or tuple(images.shape) != (total, 3)):
+        raise _lib.XrError('ms_rays: images [%d,3] fp32 on the device (got %r %s)' % (total, tuple(images.shape), images.dtype))
+    if (idx is None) == (image is None):
+        raise _lib.XrError('ms_rays: exactly one of idx / image')
+    if idx is not None:
+        if not isinstance(idx, torch.Tensor) or not _on_device(idx) or idx.dtype != torch.int64 or idx.dim() != 1:
+            raise _lib.XrError('ms_rays: idx [R] int64 on the device')
+        rays, image, first_pixel = int(idx.shape[0]), 0, 0
+    else:
+        image, first_pixel = int(image), int(first_pixel)
+        if not 0 <= image < n:
+            raise _lib.XrError('ms_rays: image %d of %d' % (image, n))
+        frame = int(sizes[image][0]) * int(sizes[image][1])
+        rays = frame - first_pixel if R is None else int(R)
+        if first_pixel < 0 or rays < 0 or first_pixel + rays > frame:
+            raise _lib.XrError('ms_rays: pixels %d .. %d of a frame of %d' % (first_pixel, first_pixel + rays, frame))
+    if t_rand is not None and (S < 1 or t_rand.dtype != torch.float32 or tuple(t_rand.shape) != (rays, S) or not _on_device(t_rand)):
+        raise _lib.XrError('ms_rays: t_rand [R,S] fp32 (got %r %s at R %d S %d)' % (tuple(t_rand.shape), t_rand.dtype, rays, S))
+    have = {'rays_o': (rays, 3), 'rays_d': (rays, 3), 'viewdirs': (rays, 3), 'radii': (rays, 1), 'lossmult': (rays, 1), 'near': (rays, 1), 'far': (rays, 1)}
+    if S >= 1:
+        have['z_vals'] = (rays, S)
+    if images is not None:
+        have['target_s'] = (rays, 3)
+    if want is not None and [k for k in want if k not in have]:
+        raise _lib.XrError('ms_rays: %r asked for, the arguments give %r' % (list(want), list(have)))
+    out = {k: torch.empty(have[k], dtype=torch.float32, device=dev) for k in MS_OUTPUTS if k in have and (want is None or k in want)}
+    if rays == 0:               # nothing to launch (and an empty tensor has no pointer to hand over)
+        return out
+    cont = lambda t: None if t is None else (t if t.is_contiguous() else t.contiguous())
+    cams, hw, prefix, images, idx, t_rand = cont(cams), cont(hw), cont(prefix), cont(images), cont(idx), cont(t_rand)
+    with _span('xr_ms_rays', rays * max(S, 1), train=False):
+        _lib.check(_lib.load().xr_ms_rays(_ptr(cams), _ptr(hw), _ptr(prefix), n, total, _ptr(images), _ptr(idx), image, first_pixel, rays, S,
+                                         int(bool(lindisp)), _ptr(t_rand), *[_ptr(out.get(k)) for k in MS_OUTPUTS], _stream()), 'xr_ms_rays')
+    return out
+
+
+def ms_pyramid_sizes(H, W, n_down):
+    """[(H >> j, W >> j)] of the n_down levels; ValueError when the base does not halve n_down - 1 times (the reference's reshape raises)"""
+    H, W, n_down = int(H), int(W), int(n_down)
+    if not 1 <= n_down <= MS_MAX_DOWN:
+        raise ValueError('ms_pyramid: n_down must be 1 .. %d (got %d)' % (MS_MAX_DOWN, n_down))
+    if min(H, W) < 1 or H % (1 << (n_down - 1)) or W % (1 << (n_down - 1)):
+        raise ValueError('ms_pyramid: a %d x %d image cannot be halved %d times' % (H, W, n_down - 1))
+    return [(H >> j, W >> j) for j in range(n_down)]
+
+
+def ms_pyramid(base, n_down, white_bkgd=True, want=('bytes', 'pixels')):
+    """the multiscale converter's image side (xrnerf_mi355_multiscale.h): base [N,H,W,C] uint8 device tensor (C = 3 or 4) ->
+    {'bytes': [N per_view, C] uint8 (what the converter saves), 'pixels': [N per_view, 3] fp32 (what load_multiscale_data loads)}, packed
+    view-major with a view's levels consecutive; per_view = sum of the level sizes (ms_pyramid_sizes)."""
+    if not isinstance(base, torch.Tensor) or not _on_device(base) or base.dtype != torch.uint8 or base.dim() != 4 or base.shape[3] not in (3, 4):
+        raise _lib.XrError('ms_pyramid: base must be a [N,H,W,3 or 4] uint8 ROCm device tensor: there is no CPU fallback')
+    N, H, W, Cn = (int(v) for v in base.shape)
+    per_view = sum(h * w for h, w in ms_pyramid_sizes(H, W, n_down))
+    out = {}
+    if 'bytes' in want:
+        out['bytes'] = torch.empty((N * per_view, Cn), dtype=torch.uint8, device=base.device)
+    if 'pixels' in want:
+        out['pixels'] = torch.empty((N * per_view, 3), dtype=torch.float32, device=base.device)
+    if not out:
+        raise _lib.XrError('ms_pyramid: nothing asked for')
+    if N == 0:
+        return out
+    base = base if base.is_contiguous() else base.contiguous()
+    with _span('xr_ms_pyramid', N * per_view, train=False):
+        _lib.check(_lib.load().xr_ms_pyramid(_ptr(base), N, H, W, Cn, int(n_down), int(bool(white_bkgd)), _ptr(out.get('bytes')), _ptr(out.get('pixels')),
+                                            _stream()), 'xr_ms_pyramid')
+    return out

@@ -397,7 +397,8 @@ class _FusedRun:
 @PIPELINES.register_module()
 class Compose:
     """a sequence of transforms (config dicts or callables); returns None when a transform does (compose.py:20-45).  `fuse = False`
-    forces the step-by-step tensor-op path (the timing baseline of tools/microbench_pipeline.py)."""
+    forces the step-by-step tensor-op path (the timing baseline of tools/microbench_pipeline.py).  A list _FusedRun.plan leaves alone
+    is offered to multiscale.MultiscaleRun.plan (the Mip-NeRF multiscale lists over a camera table)."""
 
     def __init__(self, transforms):
         assert isinstance(transforms, Sequence)
@@ -409,6 +410,9 @@ class Compose:
                 raise TypeError('transform must be callable or a dict, but got %s' % type(transform))
             self.transforms.append(transform)
         self.fused = _FusedRun.plan(self.transforms)
+        if self.fused is None:              # the second planner: [MipMultiScaleSample, GetZvals, ToTensor ...] over a camera table
+            from . import multiscale
+            self.fused = multiscale.MultiscaleRun.plan(self.transforms)
         self.fuse = True
 
     def __call__(self, data):
@@ -572,3 +576,6 @@ class PassIterHook:
     def after_train_iter(self, runner):
         dataset = self.dataset if self.dataset is not None else runner.data_loader.iter_loader._dataset
         dataset.set_iter(runner.iter)
+
+
+from . import multiscale  # noqa: E402,F401  (registers MipMultiScaleSample and MipMultiScaleDataset: the data side of mipnerf_multiscale.py)
