@@ -290,6 +290,18 @@ MULTISCALE_SIGNATURES = {
     'xr_ms_pyramid': (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp]),
 }
 
+# ZJU-MoCap / H36M human data (csrc/xr_bodydata.hip, declared in include/xrnerf_mi355_bodydata.h): a table of its own as well
+BODYDATA_SIGNATURES = {
+    'xr_body_prepare': (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _i32, _vp, _vp, _vp]),
+    'xr_body_masks_workspace_bytes': (_sz, [_u32, _u32]),
+    'xr_body_masks': (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'xr_body_sample': (_i32, [_vp, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xr_body_points': (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    'xr_body_frame_workspace_bytes': (_sz, [_u32, _u32]),
+    'xr_body_frame_count': (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp]),
+    'xr_body_frame_write': (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -348,7 +360,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()):
+            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

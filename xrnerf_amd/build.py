@@ -69,6 +69,10 @@ SOURCES = {
     # Mip-NeRF multiscale data (ray sampler over a camera table, box pyramid): the rays are double arithmetic in the reference's operation
     # order, rounded to fp32 once, and the pyramid is (((a + b) + c) + d) / 4 in fp32 -- bit for bit numpy's results, nothing fused
     'xr_multiscale.hip': ['-ffp-contract=off'],
+    # ZJU-MoCap / H36M human data (prepared pictures, box silhouette lists, body-box ray sampler): the rays and the box test are double
+    # arithmetic in the reference's operation order, rounded to fp32 once, the undistortion map is double whose floor picks the bilinear
+    # taps, z_vals and pts are un-fused fp32 -- bit for bit numpy's and torch's results, nothing fused
+    'xr_bodydata.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

@@ -2844,3 +2844,170 @@ def ms_pyramid(base, n_down, white_bkgd=True, want=('bytes', 'pixels')):
         _lib.check(_lib.load().xr_ms_pyramid(_ptr(base), N, H, W, Cn, int(n_down), int(bool(white_bkgd)), _ptr(out.get('bytes')), _ptr(out.get('pixels')),
                                             _stream()), 'xr_ms_pyramid')
     return out
+
+
+# ---------------------------------------------------------------- ZJU-MoCap / H36M human data (csrc/xr_bodydata.hip)
+BODY_CAM_DOUBLES = 30           # XR_BODY_CAM_DOUBLES: inv(K) (9), R (9), T (3), rays_o (3), bounds min (3), bounds max (3)
+BODY_ROUNDS = 8                 # XR_BODY_ROUNDS
+BODY_MAX_SEL = 65536            # XR_BODY_MAX_SEL
+BODY_MAX_SHRINK = 16            # XR_BODY_MAX_SHRINK
+_BODY_ENTRIES = ('xr_body_prepare', 'xr_body_masks', 'xr_body_sample', 'xr_body_points', 'xr_body_frame_count', 'xr_body_frame_write')
+
+
+def bodydata_kernels_available():
+    """the loaded library handle has xr_bodydata.hip's entry points (see gnr_kernels_available)"""
+    lib = _lib.load()
+    return all(hasattr(lib, name) for name in _BODY_ENTRIES)
+
+
+def _body_dev(t, dtype, shape, what):
+    if not isinstance(t, torch.Tensor) or not _on_device(t) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise _lib.XrError('%s must be a %s ROCm device tensor%s: there is no CPU fallback' % (what, dtype, '' if shape is None else ' of shape %r' % (tuple(shape),)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def body_shrink(ratio):
+    """the integer s = 1 / ratio the block mean is defined for; anything else is refused by name"""
+    s = int(round(1. / float(ratio))) if float(ratio) > 0 else 0
+    if s < 1 or s > BODY_MAX_SHRINK or abs(s * float(ratio) - 1.) > 1e-12:
+        raise NotImplementedError('body_prepare: ratio %r is not supported (1 / ratio must be an integer 1 .. %d)' % (ratio, BODY_MAX_SHRINK))
+    return s
+
+
+def body_prepare(img8, msk8, K, D, ratio, white_bkgd):
+    """the prepared picture (xrnerf_mi355_bodydata.h): img8 [Hs,Ws,3] and msk8 [Hm,Wm] uint8 device tensors, K [3,3] (unscaled) and D (5)
+    host values -> (img [H,W,3] fp32, msk [H,W] uint8) on the device, H = Hs ratio, W = Ws ratio.  One launch, nothing read back."""
+    s = body_shrink(ratio)
+    img8, msk8 = _body_dev(img8, torch.uint8, None, 'body_prepare: img8'), _body_dev(msk8, torch.uint8, None, 'body_prepare: msk8')
+    if img8.dim() != 3 or img8.shape[2] != 3 or msk8.dim() != 2:
+        raise _lib.XrError('body_prepare: img8 [Hs,Ws,3] and msk8 [Hm,Wm] (got %r, %r)' % (tuple(img8.shape), tuple(msk8.shape)))
+    Hs, Ws = int(img8.shape[0]), int(img8.shape[1])
+    if Hs % s or Ws % s:
+        raise ValueError('body_prepare: a %d x %d picture cannot be shrunk by %d' % (Hs, Ws, s))
+    kd = np.concatenate([np.asarray(K, np.float64).reshape(9), np.asarray(D, np.float64).reshape(-1)[:5]])
+    if kd.shape[0] != 14:
+        raise _lib.XrError('body_prepare: K [3,3] and D of 5 coefficients')
+    img = torch.empty((Hs // s, Ws // s, 3), dtype=torch.float32, device=img8.device)
+    msk = torch.empty((Hs // s, Ws // s), dtype=torch.uint8, device=img8.device)
+    with _span('xr_body_prepare', img.numel() // 3, train=False):
+        _lib.check(_lib.load().xr_body_prepare(_ptr(img8), _ptr(msk8), Hs, Ws, int(msk8.shape[0]), int(msk8.shape[1]), kd.ctypes.data_as(C.c_void_p), s,
+                                              int(bool(white_bkgd)), _ptr(img), _ptr(msk), _stream()), 'xr_body_prepare')
+    return img, msk
+
+
+def body_masks(msk, corners):
+    """the two candidate lists of a prepared picture: msk [H,W] uint8 device tensor, corners [8,2] host integers (x, y) ->
+    (bound_list, body_list) int32 device tensors in argwhere order.  ONE blocking read, of the two lengths (made once per picture)."""
+    msk = _body_dev(msk, torch.uint8, None, 'body_masks: msk')
+    if msk.dim() != 2:
+        raise _lib.XrError('body_masks: msk [H,W]')
+    H, W = int(msk.shape[0]), int(msk.shape[1])
+    c = np.ascontiguousarray(np.asarray(corners).reshape(16), dtype=np.int64)
+    if np.abs(c).max() > (1 << 30):
+        raise ValueError('body_masks: a projected corner lies beyond +-2^30 pixels')
+    c = c.astype(np.int32)
+    lib = _lib.load()
+    nbytes = int(lib.xr_body_masks_workspace_bytes(H, W))
+    ws = _ws(msk.device, nbytes, 'bodymasks')
+    bound = torch.empty(H * W, dtype=torch.int32, device=msk.device)
+    body = torch.empty(H * W, dtype=torch.int32, device=msk.device)
+    totals = torch.empty(2, dtype=torch.int32, device=msk.device)
+    with _span('xr_body_masks', H * W, train=False):
+        _lib.check(lib.xr_body_masks(_ptr(msk), H, W, c.ctypes.data_as(C.c_void_p), _ptr(bound), _ptr(body), _ptr(totals), _ptr(ws), nbytes, _stream()),
+                   'xr_body_masks')
+    nb, nh = (int(v) for v in totals.tolist())
+    if nb < 0 or nh < 0:
+        raise _lib.XrError('body_masks: a list total beyond int32')
+    return bound[:nb].clone(), body[:nh].clone()
+
+
+def body_sample(cam, H, W, img, body_list, bound_list, draws, short_items, S=0, t_rand=None, fused_points=False, want_target=True):
+    """one training item (xrnerf_mi355_bodydata.h) -> dict of fp32 device tensors rays_o, rays_d [n,3], near, far [n,1], target_s [n,3],
+    and with S >= 1 z_vals [n,S], pts [n,S,3].  cam [30] double, img [H,W,3] fp32, the lists int32, draws [8,n] int64, short_items [1]
+    uint32 (the persistent counter): device tensors.  fused_points: z_vals and pts by the sampling workgroup itself (one launch) instead
+    of a second wide launch.  Empty lists raise ValueError before anything is launched.  Nothing is read back."""
+    H, W, S = int(H), int(W), int(S)
+    cam = _body_dev(cam, torch.float64, (BODY_CAM_DOUBLES,), 'body_sample: cam')
+    body_list = _body_dev(body_list, torch.int32, None, 'body_sample: body_list')
+    bound_list = _body_dev(bound_list, torch.int32, None, 'body_sample: bound_list')
+    draws = _body_dev(draws, torch.int64, None, 'body_sample: draws')
+    short_items = _body_dev(short_items, torch.int32, (1,), 'body_sample: short_items')
+    if draws.dim() != 2 or draws.shape[0] != BODY_ROUNDS:
+        raise _lib.XrError('body_sample: draws [%d, sel_n] int64 (got %r)' % (BODY_ROUNDS, tuple(draws.shape)))
+    n = int(draws.shape[1])
+    if body_list.numel() == 0 or bound_list.numel() == 0:
+        raise ValueError('body_sample: an empty candidate list (body %d, bound %d): the reference\'s randint(0, 0) raises too' % (body_list.numel(), bound_list.numel()))
+    if want_target:
+        img = _body_dev(img, torch.float32, (H, W, 3), 'body_sample: img')
+    if t_rand is not None:
+        t_rand = _body_dev(t_rand, torch.float32, (n, S), 'body_sample: t_rand')
+    dev = cam.device
+    out = {'rays_o': torch.empty((n, 3), dtype=torch.float32, device=dev), 'rays_d': torch.empty((n, 3), dtype=torch.float32, device=dev),
+           'near': torch.empty((n, 1), dtype=torch.float32, device=dev), 'far': torch.empty((n, 1), dtype=torch.float32, device=dev)}
+    if want_target:
+        out['target_s'] = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    zp = {}
+    if S >= 1:
+        zp = {'z_vals': torch.empty((n, S), dtype=torch.float32, device=dev), 'pts': torch.empty((n, S, 3), dtype=torch.float32, device=dev)}
+    inside = bool(fused_points) and S >= 1
+    with _span('xr_body_sample', n * (S if inside else 1), train=False):
+        _lib.check(_lib.load().xr_body_sample(_ptr(cam), H, W, _ptr(img) if want_target else None, _ptr(body_list), int(body_list.numel()), _ptr(bound_list),
+                                             int(bound_list.numel()), _ptr(draws), n, S if inside else 0, _ptr(t_rand) if inside else None,
+                                             _ptr(out['rays_o']), _ptr(out['rays_d']), _ptr(out['near']), _ptr(out['far']), _ptr(out.get('target_s')),
+                                             _ptr(zp.get('z_vals')) if inside else None, _ptr(zp.get('pts')) if inside else None, _ptr(short_items),
+                                             _stream()), 'xr_body_sample')
+    if S >= 1 and not inside:
+        with _span('xr_body_points', n * S, train=False):
+            _lib.check(_lib.load().xr_body_points(_ptr(out['rays_o']), _ptr(out['rays_d']), _ptr(out['near']), _ptr(out['far']), n, S, _ptr(t_rand),
+                                                 _ptr(zp['z_vals']), _ptr(zp['pts']), _stream()), 'xr_body_points')
+    out.update(zp)
+    return out
+
+
+def body_points(rays_o, rays_d, near, far, S, t_rand=None):
+    """z_vals [R,S] and pts [R,S,3] of R rays with per-ray near / far (xr_body_points): one launch"""
+    S, R = int(S), int(rays_o.shape[0])
+    rays_o, rays_d = _body_dev(rays_o, torch.float32, (R, 3), 'body_points: rays_o'), _body_dev(rays_d, torch.float32, (R, 3), 'body_points: rays_d')
+    near, far = _body_dev(near, torch.float32, (R, 1), 'body_points: near'), _body_dev(far, torch.float32, (R, 1), 'body_points: far')
+    if S < 1:
+        raise _lib.XrError('body_points: S >= 1')
+    if t_rand is not None:
+        t_rand = _body_dev(t_rand, torch.float32, (R, S), 'body_points: t_rand')
+    out = {'z_vals': torch.empty((R, S), dtype=torch.float32, device=rays_o.device), 'pts': torch.empty((R, S, 3), dtype=torch.float32, device=rays_o.device)}
+    if R == 0:
+        return out
+    with _span('xr_body_points', R * S, train=False):
+        _lib.check(_lib.load().xr_body_points(_ptr(rays_o), _ptr(rays_d), _ptr(near), _ptr(far), R, S, _ptr(t_rand), _ptr(out['z_vals']), _ptr(out['pts']),
+                                             _stream()), 'xr_body_points')
+    return out
+
+
+def body_frame(cam, H, W, img=None):
+    """a whole frame (NBSelectRays(sel_all=True)) -> dict: mask_at_box [H W] bool, rays_o, rays_d [M,3], near, far [M,1], target_s [M,3]
+    (img given), the M survivors in nonzero order.  ONE blocking read, of M."""
+    H, W = int(H), int(W)
+    cam = _body_dev(cam, torch.float64, (BODY_CAM_DOUBLES,), 'body_frame: cam')
+    if img is not None:
+        img = _body_dev(img, torch.float32, (H, W, 3), 'body_frame: img')
+    if min(H, W) < 1 or H * W > 0x7fffffff:
+        raise _lib.XrError('body_frame: H, W >= 1 and H W within int32 (got %d x %d)' % (H, W))
+    lib, dev = _lib.load(), cam.device
+    nbytes = int(lib.xr_body_frame_workspace_bytes(H, W))
+    ws = _ws(dev, nbytes, 'bodyframe')
+    mask = torch.empty(H * W, dtype=torch.uint8, device=dev)
+    total = torch.empty(1, dtype=torch.int32, device=dev)
+    with _span('xr_body_frame_count', H * W, train=False):
+        _lib.check(lib.xr_body_frame_count(_ptr(cam), H, W, _ptr(mask), _ptr(total), _ptr(ws), nbytes, _stream()), 'xr_body_frame_count')
+    M = int(total.item())
+    if M < 0:
+        raise _lib.XrError('body_frame: the survivor count does not fit int32')
+    out = {'mask_at_box': mask.view(torch.bool),
+           'rays_o': torch.empty((M, 3), dtype=torch.float32, device=dev), 'rays_d': torch.empty((M, 3), dtype=torch.float32, device=dev),
+           'near': torch.empty((M, 1), dtype=torch.float32, device=dev), 'far': torch.empty((M, 1), dtype=torch.float32, device=dev)}
+    if img is not None:
+        out['target_s'] = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    if M:
+        with _span('xr_body_frame_write', M, train=False):
+            _lib.check(lib.xr_body_frame_write(_ptr(cam), H, W, _ptr(img), _ptr(mask), _ptr(ws), nbytes, M, _ptr(out['rays_o']), _ptr(out['rays_d']),
+                                              _ptr(out['near']), _ptr(out['far']), _ptr(out.get('target_s')), _stream()), 'xr_body_frame_write')
+    return out

@@ -398,7 +398,8 @@ class _FusedRun:
 class Compose:
     """a sequence of transforms (config dicts or callables); returns None when a transform does (compose.py:20-45).  `fuse = False`
     forces the step-by-step tensor-op path (the timing baseline of tools/microbench_pipeline.py).  A list _FusedRun.plan leaves alone
-    is offered to multiscale.MultiscaleRun.plan (the Mip-NeRF multiscale lists over a camera table)."""
+    is offered to multiscale.MultiscaleRun.plan (the Mip-NeRF multiscale lists over a camera table), then to bodydata.BodyRun.plan (the
+    NeuralBody / Animatable NeRF lists over a prepared picture)."""
 
     def __init__(self, transforms):
         assert isinstance(transforms, Sequence)
@@ -413,6 +414,9 @@ class Compose:
         if self.fused is None:              # the second planner: [MipMultiScaleSample, GetZvals, ToTensor ...] over a camera table
             from . import multiscale
             self.fused = multiscale.MultiscaleRun.plan(self.transforms)
+        if self.fused is None:              # the third planner: [NBGetRays, NBSelectRays, ToTensor, GetZvals ...] over a prepared picture
+            from . import bodydata
+            self.fused = bodydata.BodyRun.plan(self.transforms)
         self.fuse = True
 
     def __call__(self, data):
@@ -579,3 +583,4 @@ class PassIterHook:
 
 
 from . import multiscale  # noqa: E402,F401  (registers MipMultiScaleSample and MipMultiScaleDataset: the data side of mipnerf_multiscale.py)
+from . import bodydata  # noqa: E402,F401  (registers NeuralBodyDataset, AniNeRFDataset and their seven transforms: the data side of nb_zjumocap_*.py / an_*.py)
