@@ -302,6 +302,14 @@ BODYDATA_SIGNATURES = {
     'xr_body_frame_write': (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# GeneBody data (csrc/xr_genebody.hip, declared in include/xrnerf_mi355_genebody.h): a table of its own as well
+GENEBODY_SIGNATURES = {
+    'xr_gb_crop_box': (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    'xr_gb_resize': (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    'xr_gb_assemble': (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'xr_gb_calib': (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -360,7 +368,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()):
+            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()) + list(GENEBODY_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -73,6 +73,10 @@ SOURCES = {
     # arithmetic in the reference's operation order, rounded to fp32 once, the undistortion map is double whose floor picks the bilinear
     # taps, z_vals and pts are un-fused fp32 -- bit for bit numpy's and torch's results, nothing fused
     'xr_bodydata.hip': ['-ffp-contract=off'],
+    # GeneBody data (crop box, OpenCV's nearest and 8-bit fixed-point cubic resize, a view in its role, camera rows): the crop rule and the
+    # resize coordinates are double, the cubic coefficients, the adjusted K and the pixels are fp32, each written in explicitly rounded
+    # single operations in the reference's order -- bit for bit numpy's and torch's results, nothing fused
+    'xr_genebody.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

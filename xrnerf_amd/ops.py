@@ -3011,3 +3011,131 @@ def body_frame(cam, H, W, img=None):
             _lib.check(lib.xr_body_frame_write(_ptr(cam), H, W, _ptr(img), _ptr(mask), _ptr(ws), nbytes, M, _ptr(out['rays_o']), _ptr(out['rays_d']),
                                               _ptr(out['near']), _ptr(out['far']), _ptr(out.get('target_s')), _stream()), 'xr_body_frame_write')
     return out
+
+
+# ---------------------------------------------------------------- GeneBody data (csrc/xr_genebody.hip)
+GB_MAX_VIEWS = 64               # XR_GB_MAX_VIEWS
+GB_MAX_DIST = 8                 # XR_GB_MAX_DIST
+_GB_ENTRIES = ('xr_gb_crop_box', 'xr_gb_resize', 'xr_gb_assemble', 'xr_gb_calib')
+
+
+def genebody_kernels_available():
+    """the loaded library handle has xr_genebody.hip's entry points (see gnr_kernels_available)"""
+    lib = _lib.load()
+    return all(hasattr(lib, name) for name in _GB_ENTRIES)
+
+
+def gb_pack(arrays, dtype, device, align=16):
+    """host arrays -> (one device tensor holding them back to back, each on `align` bytes; their ELEMENT offsets)"""
+    item = np.dtype(dtype).itemsize
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += -(-a.size * item // align) * align // item
+    flat = np.zeros(max(total, 1), dtype)
+    for a, o in zip(arrays, offs):
+        flat[o:o + a.size] = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    if flat.dtype == np.uint16:
+        flat = flat.view(np.int16)          # the bits travel as int16: the kernel reads them as uint16
+    return torch.from_numpy(flat).to(device), offs
+
+
+def _gb_ptrs(tensors):
+    """a host array of device pointers (the entry points copy it into their kernel arguments)"""
+    return (C.c_void_p * len(tensors))(*[_ptr(t).value for t in tensors])
+
+
+def gb_crop_box(masks, device=None):
+    """the crop boxes of raw masks: a list of host uint8 [h,w] arrays, or (device bytes, [(offset, h, w)]) -> [n,4] int32 device tensor
+    (top, left, bottom, right).  ONE launch, nothing read back."""
+    if isinstance(masks, tuple):
+        flat, entries = masks
+    else:
+        flat, offs = gb_pack(masks, np.uint8, device)
+        entries = [(o, m.shape[0], m.shape[1]) for o, m in zip(offs, masks)]
+    flat = _body_dev(flat, torch.uint8, None, 'gb_crop_box: masks')
+    n = len(entries)
+    if n < 1 or n > GB_MAX_VIEWS:
+        raise _lib.XrError('gb_crop_box: 1 .. %d masks a launch (got %d)' % (GB_MAX_VIEWS, n))
+    for o, h, w in entries:
+        if o < 0 or o + h * w > flat.numel():
+            raise _lib.XrError('gb_crop_box: a mask of %d x %d at %d leaves the buffer of %d bytes' % (h, w, o, flat.numel()))
+    table = np.ascontiguousarray(np.array(entries, np.int64).reshape(n, 3))
+    boxes = torch.empty((n, 4), dtype=torch.int32, device=flat.device)
+    with _span('xr_gb_crop_box', n, train=False):
+        _lib.check(_lib.load().xr_gb_crop_box(_ptr(flat), table.ctypes.data_as(C.c_void_p), n, _ptr(boxes), _stream()), 'xr_gb_crop_box')
+    return boxes
+
+
+def gb_resize(imgs, masks, depths, entries, boxes, S):
+    """the resized planes of n views.  imgs, masks: device uint8 buffers, depths: device int16 buffer holding uint16 bits (or None);
+    entries: [(img_off, mask_off, depth_off or -1, h, w)] in elements; boxes [n,4] int32 device -> (rgb [n,S,S,3] uint8, m8 [n,S,S] uint8,
+    depth [n,S,S] fp32 or None).  ONE launch, nothing read back."""
+    S, n = int(S), len(entries)
+    imgs, masks = _body_dev(imgs, torch.uint8, None, 'gb_resize: imgs'), _body_dev(masks, torch.uint8, None, 'gb_resize: masks')
+    boxes = _body_dev(boxes, torch.int32, (n, 4), 'gb_resize: boxes')
+    any_depth = any(e[2] >= 0 for e in entries)
+    if any_depth:
+        depths = _body_dev(depths, torch.int16, None, 'gb_resize: depths')
+    if n < 1 or n > GB_MAX_VIEWS:
+        raise _lib.XrError('gb_resize: 1 .. %d views a launch (got %d)' % (GB_MAX_VIEWS, n))
+    for io, mo, do, h, w in entries:
+        if io < 0 or mo < 0 or io + h * w * 3 > imgs.numel() or mo + h * w > masks.numel() or (do >= 0 and do + h * w > depths.numel()):
+            raise _lib.XrError('gb_resize: a view of %d x %d leaves its buffer' % (h, w))
+    table = np.ascontiguousarray(np.array(entries, np.int64).reshape(n, 5))
+    dev = imgs.device
+    rgb = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
+    m8 = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    depth = torch.zeros((n, S, S), dtype=torch.float32, device=dev) if any_depth else None
+    with _span('xr_gb_resize', n * S * S, train=False):
+        _lib.check(_lib.load().xr_gb_resize(_ptr(imgs), _ptr(masks), _ptr(depths) if any_depth else None, table.ctypes.data_as(C.c_void_p), n, _ptr(boxes), S,
+                                           _ptr(rgb), _ptr(m8), _ptr(depth), _stream()), 'xr_gb_resize')
+    return rgb, m8, depth
+
+
+def gb_assemble(rgb, m8, depth, num_views, S, white_bkgd):
+    """one item's V views in their roles.  rgb, m8: lists of V device tensors ([S,S,3], [S,S] uint8); depth: list of num_views fp32 [S,S]
+    device tensors or None -> (img [V,3,S,S], mask [num_views,1,S,S], smpl_depth [num_views,S,S] or None, acc [2,V,2] int32).
+    Two memsets and ONE launch, nothing read back."""
+    V, S, num_views = len(rgb), int(S), int(num_views)
+    if V < 1 or V > GB_MAX_VIEWS or len(m8) != V or num_views > V or (depth is not None and len(depth) != num_views):
+        raise _lib.XrError('gb_assemble: 1 .. %d views, as many masks, num_views depth maps' % GB_MAX_VIEWS)
+    rgb = [_body_dev(t, torch.uint8, (S, S, 3), 'gb_assemble: rgb') for t in rgb]
+    m8 = [_body_dev(t, torch.uint8, (S, S), 'gb_assemble: m8') for t in m8]
+    if depth is not None:
+        depth = [_body_dev(t, torch.float32, (S, S), 'gb_assemble: depth') for t in depth]
+    dev = rgb[0].device
+    img = torch.empty((V, 3, S, S), dtype=torch.float32, device=dev)
+    mask = torch.empty((num_views, 1, S, S), dtype=torch.float32, device=dev)
+    smpl_depth = torch.empty((num_views, S, S), dtype=torch.float32, device=dev) if depth is not None else None
+    acc = torch.empty((2, V, 2), dtype=torch.int32, device=dev)
+    with _span('xr_gb_assemble', V * S * S, train=False):
+        _lib.check(_lib.load().xr_gb_assemble(_gb_ptrs(rgb), _gb_ptrs(m8), _gb_ptrs(depth) if depth is not None else None, V, num_views, S, int(bool(white_bkgd)),
+                                             _ptr(img), _ptr(mask), _ptr(smpl_depth), _ptr(acc), _stream()), 'xr_gb_assemble')
+    return img, mask, smpl_depth, acc
+
+
+def gb_calib(verts, K, D, w2c, crops, acc, num_views, S):
+    """one item's camera rows and scalars.  verts [N,3], K [V,3,3], D [V,nd], w2c [V,4,4] fp32 device tensors, crops: list of V int32 [4]
+    device tensors, acc: gb_assemble's -> dict persps [V,4+nd+2] fp32, vboxes [V,4] int32, sf_views [num_views] fp64, bbox [4] fp64,
+    spatial_freq [] fp64, center [3] fp32.  ONE launch, nothing read back."""
+    V, S, num_views = len(crops), int(S), int(num_views)
+    verts = _body_dev(verts, torch.float32, None, 'gb_calib: verts')
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise _lib.XrError('gb_calib: verts [N,3] with N >= 1')
+    K, w2c = _body_dev(K, torch.float32, (V, 3, 3), 'gb_calib: K'), _body_dev(w2c, torch.float32, (V, 4, 4), 'gb_calib: w2c')
+    D = _body_dev(D, torch.float32, None, 'gb_calib: D')
+    nd = int(D.numel() // V) if V else 0
+    if V < 2 or V > GB_MAX_VIEWS or not 1 <= num_views < V or D.numel() != V * nd or nd > GB_MAX_DIST:
+        raise _lib.XrError('gb_calib: 2 .. %d views, 1 <= num_views < V, at most %d distortion coefficients' % (GB_MAX_VIEWS, GB_MAX_DIST))
+    crops = [_body_dev(t, torch.int32, (4,), 'gb_calib: crop') for t in crops]
+    acc = _body_dev(acc, torch.int32, (2, V, 2), 'gb_calib: acc')
+    dev = verts.device
+    out = {'persps': torch.empty((V, 4 + nd + 2), dtype=torch.float32, device=dev), 'vboxes': torch.empty((V, 4), dtype=torch.int32, device=dev),
+           'sf_views': torch.empty(num_views, dtype=torch.float64, device=dev), 'bbox': torch.empty(4, dtype=torch.float64, device=dev),
+           'spatial_freq': torch.empty((), dtype=torch.float64, device=dev), 'center': torch.empty(3, dtype=torch.float32, device=dev)}
+    with _span('xr_gb_calib', V * int(verts.shape[0]), train=False):
+        _lib.check(_lib.load().xr_gb_calib(_ptr(verts), int(verts.shape[0]), _ptr(K), _ptr(D), nd, _ptr(w2c), _gb_ptrs(crops), _ptr(acc), V, num_views, S,
+                                          _ptr(out['persps']), _ptr(out['vboxes']), _ptr(out['sf_views']), _ptr(out['bbox']), _ptr(out['spatial_freq']),
+                                          _ptr(out['center']), _stream()), 'xr_gb_calib')
+    return out

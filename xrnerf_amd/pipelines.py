@@ -584,3 +584,4 @@ class PassIterHook:
 
 from . import multiscale  # noqa: E402,F401  (registers MipMultiScaleSample and MipMultiScaleDataset: the data side of mipnerf_multiscale.py)
 from . import bodydata  # noqa: E402,F401  (registers NeuralBodyDataset, AniNeRFDataset and their seven transforms: the data side of nb_zjumocap_*.py / an_*.py)
+from . import genebody  # noqa: E402,F401  (registers GeneBodyDataset: the data side of gnr_genebody.py)
