@@ -310,6 +310,13 @@ GENEBODY_SIGNATURES = {
     'xr_gb_calib': (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# BungeeNeRF data (csrc/xr_bungeedata.hip, declared in include/xrnerf_mi355_bungeedata.h): a table of its own as well
+BUNGEEDATA_SIGNATURES = {
+    'xr_bgd_item': (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _d, _f, _f, _vp, _u64, _u64, _u32, _i32, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _vp, _vp, _vp]),
+    'xr_bgd_frame': (_i32, [_vp, _u32, _u32, _f, _f, _f, _f, _u32, _i32, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -368,7 +375,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(BUNGEE_SIGNATURES.items()) + list(VANILLA_SIGNATURES.items()) + \
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()) + list(GENEBODY_SIGNATURES.items()):
+            list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()) + list(GENEBODY_SIGNATURES.items()) + \
+            list(BUNGEEDATA_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

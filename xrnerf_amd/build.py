@@ -77,6 +77,9 @@ SOURCES = {
     # resize coordinates are double, the cubic coefficients, the adjusted K and the pixels are fp32, each written in explicitly rounded
     # single operations in the reference's order -- bit for bit numpy's and torch's results, nothing fused
     'xr_genebody.hip': ['-ffp-contract=off'],
+    # BungeeNeRF data (a training item, a validation frame): the training rays are double arithmetic in numpy's operation order, rounded
+    # to fp32 once, the frame's rays and every bound and z-value are un-fused fp32 in torch's -- bit for bit their results, nothing fused
+    'xr_bungeedata.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

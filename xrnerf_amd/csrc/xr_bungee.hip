@@ -18,6 +18,7 @@
 // expressions the same way, not to the precision fp64 would give.
 #include "xr_common.h"
 #include "xr_mip_math.h"
+#include "xr_bungee_zvals.h"
 #include "xr_render.h"
 
 #define BG_TILE 64
@@ -29,69 +30,24 @@ struct BungeeZArgs {
     const float* rays_o; const float* viewdirs;
     float* near; float* far;                 // inputs (mode 0) or outputs (modes 1, 2)
     uint32_t n_rays, n_z;
-    int mode;                                // 0 none, 1 sphere, 2 flat
-    float cx, cy, cz;                        // float32(scene_origin * scaling)
-    float r2_top, r2_earth;                  // float32(((6371011 + 250) s)^2), float32((6371011 s)^2)
-    float s;                                 // float32(scaling)
+    BgBounds b;
     float* z_out;
 };
 
-// torch.norm(x, dim=-1) of a 3-vector: sqrt of the sequential sum of squares
-static __device__ inline float bg_norm3(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
-
-// create.py BungeeGetBounds, sphere: the smaller root of |o + t v - c|^2 = r^2 in the reference's expression order
-static __device__ inline float bg_sphere_dist(const float oc[3], const float o[3], const float v[3], float b, float nv2, float r2) {
-    const float no = bg_norm3(oc[0], oc[1], oc[2]);
-    const float tb = 2.f * b;
-    const float delta = tb * tb - 4.f * nv2 * (no * no - r2);
-    const float t = (-2.f * b - sqrtf(delta)) / (2.f * nv2);
-    // |o - (o + t v)|
-    const float e[3] = {o[0] - (o[0] + t * v[0]), o[1] - (o[1] + t * v[1]), o[2] - (o[2] + t * v[2])};
-    return bg_norm3(e[0], e[1], e[2]);
-}
-
+// the bounds, the edges and the reference's sort: xr_bungee_zvals.h (shared with xr_bungeedata.hip)
 __global__ void k_bungee_zvals(BungeeZArgs a) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.n_rays) return;
     float nr, fr;
-    if (a.mode == 0) {
+    if (a.b.mode == 0) {
         nr = a.near[r]; fr = a.far[r];
     } else {
         const float o[3] = {a.rays_o[r * 3ull], a.rays_o[r * 3ull + 1], a.rays_o[r * 3ull + 2]};
         const float v[3] = {a.viewdirs[r * 3ull], a.viewdirs[r * 3ull + 1], a.viewdirs[r * 3ull + 2]};
-        if (a.mode == 1) {
-            const float oc[3] = {o[0] - a.cx, o[1] - a.cy, o[2] - a.cz};
-            const float b = oc[0] * v[0] + oc[1] * v[1] + oc[2] * v[2];
-            const float nv = bg_norm3(v[0], v[1], v[2]);
-            const float nv2 = nv * nv;
-            nr = bg_sphere_dist(oc, o, v, b, nv2, a.r2_top) * 0.9f;
-            fr = bg_sphere_dist(oc, o, v, b, nv2, a.r2_earth) * 1.1f;
-        } else {
-            // planes z = 250 s (near) and z = 0 (far); the x / y terms of the reference's dot products are signed zeros
-            const float den = v[2] * a.s;
-            const float oz = o[2] * a.s;
-            nr = (250.f * a.s - oz) / den;
-            fr = (0.f - oz) / den;
-            nr = nr != nr ? nr : fmaxf(nr, 1e-6f);                           // clamp(min=1e-6) keeps NaN
-        }
+        bg_bounds(a.b, o, v, &nr, &fr);
         a.near[r] = nr; a.far[r] = fr;
     }
-    // BungeeGetZvals: the first n1 = floor(2N/3) edges linear in disparity, the rest linear in depth from edge n1-1 to far
-    const uint32_t N = a.n_z, n1 = (2u * N) / 3u, n2 = N - n1 + 1;
-    float* z = a.z_out + (uint64_t)r * N;
-    for (uint32_t j = 0; j < n1; ++j) z[j] = xr_mip_zval(nr, fr, N, j, 1);
-    const float start = z[n1 - 1];
-    for (uint32_t j = 1; j < n2; ++j) {
-        const float t = xr_torch_linspace(0.f, 1.f, n2, j);
-        z[n1 + j - 1] = start * (1.f - t) + fr * t;
-    }
-    // torch.sort (ascending, NaN last): insertion sort; the edges are almost always in order already, so this is one pass
-    for (uint32_t j = 1; j < N; ++j) {
-        const float v = z[j];
-        uint32_t k = j;
-        while (k > 0 && (z[k - 1] > v || (z[k - 1] != z[k - 1] && v == v))) { z[k] = z[k - 1]; --k; }
-        z[k] = v;
-    }
+    bg_zvals_row(nr, fr, a.n_z, a.z_out + (uint64_t)r * a.n_z);
 }
 
 // ------------------------------------------------------------------------------------------ cast_rays + BungeeEmbedder
@@ -274,8 +230,8 @@ extern "C" int xr_bungee_zvals(const float* rays_o, const float* viewdirs, float
     XR_REQUIRE(near && far && z_out, "null pointer");
     XR_REQUIRE(bounds_mode == 0 || (rays_o && viewdirs), "null pointer");
     XR_REQUIRE(bounds_mode != 1 || globe_center, "sphere bounds need the globe centre");
-    BungeeZArgs a{rays_o, viewdirs, near, far, n_rays, n_z, bounds_mode, 0.f, 0.f, 0.f, r2_top, r2_earth, scaling, z_out};
-    if (bounds_mode == 1) { a.cx = globe_center[0]; a.cy = globe_center[1]; a.cz = globe_center[2]; }
+    BungeeZArgs a{rays_o, viewdirs, near, far, n_rays, n_z, BgBounds{bounds_mode, 0.f, 0.f, 0.f, r2_top, r2_earth, scaling}, z_out};
+    if (bounds_mode == 1) { a.b.cx = globe_center[0]; a.b.cy = globe_center[1]; a.b.cz = globe_center[2]; }
     hipLaunchKernelGGL(k_bungee_zvals, dim3(xr_div_up(n_rays, 128)), dim3(128), 0, (hipStream_t)stream, a);
     XR_LAUNCH_CHECK();
     return XR_OK;

@@ -3139,3 +3139,91 @@ def gb_calib(verts, K, D, w2c, crops, acc, num_views, S):
                                           _ptr(out['persps']), _ptr(out['vboxes']), _ptr(out['sf_views']), _ptr(out['bbox']), _ptr(out['spatial_freq']),
                                           _ptr(out['center']), _stream()), 'xr_gb_calib')
     return out
+
+
+# ---------------------------------------------------------------- BungeeNeRF data (csrc/xr_bungeedata.hip)
+BGD_CAM_DOUBLES = 12            # XR_BGD_CAM_DOUBLES: cam2world rows 0..2
+BGD_MAX_SAMPLES = 1024          # XR_BGD_MAX_SAMPLES
+BGD_ITEM_OUTPUTS = ('rays_o', 'rays_d', 'target_s', 'radii', 'scale_code', 'viewdirs', 'near', 'far', 'z_vals')
+BGD_FRAME_OUTPUTS = ('rays_o', 'rays_d', 'radii', 'viewdirs', 'near', 'far', 'z_vals')
+
+
+def bungeedata_kernels_available():
+    """the loaded library handle has xr_bungeedata.hip's entry points (see gnr_kernels_available)"""
+    lib = _lib.load()
+    return hasattr(lib, 'xr_bgd_item') and hasattr(lib, 'xr_bgd_frame')
+
+
+def _bgd_bounds(ray_nearfar, scene_origin, scaling, S, who):
+    """the bounds arguments both entry points take, from bungee_zvals' own: (mode, globe centre, r2_top, r2_earth, scaling)"""
+    if ray_nearfar not in ('sphere', 'flat'):
+        raise _lib.XrError("%s: ray_nearfar must be 'sphere' or 'flat' (got %r)" % (who, ray_nearfar))
+    if S and not 2 <= S <= BGD_MAX_SAMPLES:
+        raise _lib.XrError('%s: 2 <= N_samples <= %d (got %d)' % (who, BGD_MAX_SAMPLES, S))
+    s = float(scaling)
+    gc = (C.c_float * 3)(*[float(v) * s for v in scene_origin])
+    return _BUNGEE_BOUNDS[ray_nearfar], gc, ((EARTH_RADIUS + 250.0) * s) ** 2, (EARTH_RADIUS * s) ** 2, s
+
+
+def bgd_item(cams, codes, images, i_train, H, W, focal, perm, start, R, S=0, ray_nearfar='sphere', scene_origin=(0., 0., 0.), scaling=1.0, t_rand=None,
+             want=None):
+    """one BungeeNeRF training item (xrnerf_mi355_bungeedata.h) -> dict: rays_o, rays_d, target_s, viewdirs [n,3], radii, near, far [n,1]
+    fp32, scale_code [n,1] int64, z_vals [n,S] (S >= 2).  cams [N,12] double, codes [N] int64, images [N,H,W,3] fp32, i_train [T] int32,
+    perm int64 [.]: device tensors.  The rays are perm[start : start + R], cut where perm ends (n <= R, as slicing gives); an entry
+    outside [0, T H W) gives a NaN ray.  want: the names to compute (default: all that apply)."""
+    H, W, S, start, R = int(H), int(W), int(S), int(start), int(R)
+    if H < 3:                    # dx[:, -2:-1] is empty below 3 rows: the reference returns fewer radii than rays
+        raise ValueError('bgd_item: H >= 3 (got %d)' % H)
+    cams = _body_dev(cams, torch.float64, None, 'bgd_item: cams')
+    N = int(cams.shape[0])
+    if cams.dim() != 2 or cams.shape[1] != BGD_CAM_DOUBLES or N < 1 or W < 1:
+        raise _lib.XrError('bgd_item: cams [N,12] with N >= 1, W >= 1')
+    codes, images = _body_dev(codes, torch.int64, (N,), 'bgd_item: codes'), _body_dev(images, torch.float32, (N, H, W, 3), 'bgd_item: images')
+    i_train, perm = _body_dev(i_train, torch.int32, None, 'bgd_item: i_train'), _body_dev(perm, torch.int64, None, 'bgd_item: perm')
+    T = int(i_train.numel())
+    if i_train.dim() != 1 or T < 1 or perm.dim() != 1 or start < 0 or R < 0:
+        raise _lib.XrError('bgd_item: i_train [T] with T >= 1, perm [.], start and R >= 0')
+    n = max(0, min(R, int(perm.shape[0]) - start))
+    have = {'rays_o': (n, 3), 'rays_d': (n, 3), 'target_s': (n, 3), 'radii': (n, 1), 'scale_code': (n, 1), 'viewdirs': (n, 3), 'near': (n, 1), 'far': (n, 1)}
+    if S >= 1:
+        have['z_vals'] = (n, S)
+    if want is not None and [k for k in want if k not in have]:
+        raise _lib.XrError('bgd_item: %r asked for, the arguments give %r' % (list(want), list(have)))
+    mode, gc, r2_top, r2_earth, s = _bgd_bounds(ray_nearfar, scene_origin, scaling, S, 'bgd_item')
+    if t_rand is not None:
+        t_rand = _body_dev(t_rand, torch.float32, (n, S), 'bgd_item: t_rand')
+    dev = cams.device
+    out = {k: torch.empty(have[k], dtype=torch.int64 if k == 'scale_code' else torch.float32, device=dev)
+           for k in BGD_ITEM_OUTPUTS if k in have and (want is None or k in want)}
+    if n == 0:                  # nothing to launch (and an empty tensor has no pointer to hand over)
+        return out
+    with _span('xr_bgd_item', n * max(S, 1), train=False):
+        _lib.check(_lib.load().xr_bgd_item(_ptr(cams), _ptr(codes), _ptr(images), _ptr(i_train), N, T, H, W, float(focal), float(W * .5), float(H * .5),
+                                          _ptr(perm), start, n, S if 'z_vals' in out else 0, mode, C.cast(gc, C.c_void_p), r2_top, r2_earth, s,
+                                          _ptr(t_rand) if 'z_vals' in out else None, *[_ptr(out.get(k)) for k in BGD_ITEM_OUTPUTS], _stream()), 'xr_bgd_item')
+    return out
+
+
+def bgd_frame(c2w, H, W, K, S=0, ray_nearfar='sphere', scene_origin=(0., 0., 0.), scaling=1.0, want=None):
+    """one BungeeNeRF validation frame (xrnerf_mi355_bungeedata.h): GetRays(include_radius=True) + FlattenRays + GetViewdirs +
+    BungeeGetBounds + BungeeGetZvals of pose c2w [3,4] fp32 (device) -> dict of fp32 device tensors rays_o, rays_d (not normalised),
+    viewdirs [H W,3], radii, near, far [H W,1], z_vals [H W,S] (S >= 2).  want: the names to compute (default: all that apply)."""
+    H, W, S = int(H), int(W), int(S)
+    if H < 3:                    # dx[-2:-1] is empty below 3 rows: the reference returns fewer radii than rays
+        raise ValueError('bgd_frame: GetRays(include_radius=True) needs H >= 3 (got %d)' % H)
+    c2w = _body_dev(c2w, torch.float32, (3, 4), 'bgd_frame: c2w')
+    if W < 1:
+        raise _lib.XrError('bgd_frame: W >= 1')
+    n = H * W
+    have = {'rays_o': (n, 3), 'rays_d': (n, 3), 'radii': (n, 1), 'viewdirs': (n, 3), 'near': (n, 1), 'far': (n, 1)}
+    if S >= 1:
+        have['z_vals'] = (n, S)
+    if want is not None and [k for k in want if k not in have]:
+        raise _lib.XrError('bgd_frame: %r asked for, the arguments give %r' % (list(want), list(have)))
+    mode, gc, r2_top, r2_earth, s = _bgd_bounds(ray_nearfar, scene_origin, scaling, S, 'bgd_frame')
+    out = {k: torch.empty(have[k], dtype=torch.float32, device=c2w.device) for k in BGD_FRAME_OUTPUTS if k in have and (want is None or k in want)}
+    with _span('xr_bgd_frame', n * max(S, 1), train=False):
+        _lib.check(_lib.load().xr_bgd_frame(_ptr(c2w), H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]), S if 'z_vals' in out else 0,
+                                           mode, C.cast(gc, C.c_void_p), r2_top, r2_earth, s, *[_ptr(out.get(k)) for k in BGD_FRAME_OUTPUTS], _stream()),
+                   'xr_bgd_frame')
+    return out

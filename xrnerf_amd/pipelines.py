@@ -142,6 +142,23 @@ class GetRays:
 
 
 @PIPELINES.register_module()
+class KilonerfGetRays(GetRays):
+    """GetRays under the name the KiloNeRF configs use (create.py:253-299).  The reference binds an external kilonerf_cuda.get_rays_d that
+    is not in its tree; the commented block beside the call is GetRays' arithmetic, which is what runs here.  expand_origin=False leaves
+    rays_o the [3] origin."""
+
+    def __init__(self, enable=True, expand_origin=True, **kwargs):
+        super().__init__(enable=enable, include_radius=False, **kwargs)
+        self.expand_origin = expand_origin
+
+    def __call__(self, results):
+        results = super().__call__(results)
+        if self.enable and not self.expand_origin:
+            results['rays_o'] = results['pose'][:3, -1].contiguous()
+        return results
+
+
+@PIPELINES.register_module()
 class SelectRays:
     """sel_n pixels of the frame (of its centre window during the first precrop_iters iterations), drawn without replacement
     (augment.py:37-76).  results['select_inds'] (indices into the window's row-major pixel list), when present, replaces the draw."""
@@ -293,7 +310,7 @@ class GetPts:
 
 # ------------------------------------------------------------------------------------------ the fused run
 # the order the reference's configs list the steps in; a run is fused only when its enabled steps come in this order
-_RANK = {GetRays: 0, BatchSample: 0, SelectRays: 1, FlattenRays: 1, GetViewdirs: 2, ToNDC: 3, GetBounds: 4, GetZvals: 5, PerturbZvals: 6, GetPts: 7}
+_RANK = {GetRays: 0, KilonerfGetRays: 0, BatchSample: 0, SelectRays: 1, FlattenRays: 1, GetViewdirs: 2, ToNDC: 3, GetBounds: 4, GetZvals: 5, PerturbZvals: 6, GetPts: 7}
 _PRODUCED = ('rays_o', 'rays_d', 'viewdirs', 'radii', 'near', 'far', 'z_vals', 'pts', 'target_s', 'src_shape')
 
 
@@ -303,7 +320,7 @@ class _FusedRun:
     def __init__(self, start, end, steps, side):
         self.start, self.end, self.side = start, end, side
         by = {type(t): t for t in steps}
-        self.rays, self.batch = by.get(GetRays), by.get(BatchSample)
+        self.rays, self.batch = by.get(GetRays) or by.get(KilonerfGetRays), by.get(BatchSample)
         self.select, self.flatten = by.get(SelectRays), by.get(FlattenRays)
         self.viewdirs, self.ndc, self.bounds = GetViewdirs in by, by.get(ToNDC), by.get(GetBounds)
         self.zvals, self.perturb, self.pts = by.get(GetZvals), PerturbZvals in by, GetPts in by
@@ -312,7 +329,7 @@ class _FusedRun:
     def plan(transforms):
         """the run of `transforms` that can be fused, or None"""
         enabled = lambda t: getattr(t, 'enable', True)
-        start = next((i for i, t in enumerate(transforms) if type(t) in (GetRays, BatchSample) and enabled(t)), None)
+        start = next((i for i, t in enumerate(transforms) if type(t) in (GetRays, KilonerfGetRays, BatchSample) and enabled(t)), None)
         ends = [i for i, t in enumerate(transforms) if type(t) in (GetZvals, PerturbZvals, GetPts) and enabled(t)]
         if start is None or not ends or ends[-1] < start:
             return None
@@ -329,6 +346,8 @@ class _FusedRun:
                 rank = _RANK[type(t)]
                 steps.append(t)
         run = _FusedRun(start, end, steps, side)
+        if not getattr(run.rays, 'expand_origin', True):           # the kernel writes one origin per ray
+            return None
         radius = run.rays is not None and run.rays.include_radius
         picker = run.select or run.flatten
         if (run.rays is not None and (picker is None or picker.include_radius != radius)) or (run.batch is not None and picker is not None):
@@ -399,7 +418,7 @@ class Compose:
     """a sequence of transforms (config dicts or callables); returns None when a transform does (compose.py:20-45).  `fuse = False`
     forces the step-by-step tensor-op path (the timing baseline of tools/microbench_pipeline.py).  A list _FusedRun.plan leaves alone
     is offered to multiscale.MultiscaleRun.plan (the Mip-NeRF multiscale lists over a camera table), then to bodydata.BodyRun.plan (the
-    NeuralBody / Animatable NeRF lists over a prepared picture)."""
+    NeuralBody / Animatable NeRF lists over a prepared picture), then to bungeedata.BungeeRun.plan (the BungeeNeRF lists)."""
 
     def __init__(self, transforms):
         assert isinstance(transforms, Sequence)
@@ -417,6 +436,9 @@ class Compose:
         if self.fused is None:              # the third planner: [NBGetRays, NBSelectRays, ToTensor, GetZvals ...] over a prepared picture
             from . import bodydata
             self.fused = bodydata.BodyRun.plan(self.transforms)
+        if self.fused is None:              # the fourth planner: [BungeeBatchSample ... BungeeGetZvals] over a BungeeState, or the frame list over a pose
+            from . import bungeedata
+            self.fused = bungeedata.BungeeRun.plan(self.transforms)
         self.fuse = True
 
     def __call__(self, data):
@@ -483,8 +505,24 @@ class SceneBaseDataset:
                 images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:])
             elif not ('load_alpha' in cfg and cfg.load_alpha):
                 images = images[..., :3]
+        elif cfg.dataset_type == 'nsvf':                           # load.py:108-143
+            from . import kilodata
+            images, poses, intrinsics, near, far, _, render_poses, (i_train, i_val, i_test) = kilodata.load_nsvf_dataset(
+                cfg.datadir, cfg.testskip, cfg.test_traj_path if 'test_traj_path' in cfg else None)
+            hwf, near, far = [intrinsics.H, intrinsics.W, intrinsics.fx], float(near), float(far)     # cx, cy, fy are not used: K is focal-centred below
+            if i_test.size == 0:
+                i_test = i_val
+            if cfg.white_bkgd and images.shape[-1] == 4:
+                images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:])
+            elif not ('load_alpha' in cfg and cfg.load_alpha):
+                images = images[..., :3]
+            render_subset = 'test' if cfg.get('render_test', False) else 'custom_path'
+            if 'render_subset' in cfg:
+                render_subset = cfg.render_subset
+            if render_subset != 'custom_path':                     # the directory has no trajectory of its own: the poses of a split
+                render_poses = np.array(poses[{'train': i_train, 'val': i_val, 'test': i_test}[render_subset]])
         else:
-            raise NotImplementedError('SceneBaseDataset: dataset_type %r is not supported (blender and llff are)' % (cfg.dataset_type,))
+            raise NotImplementedError('SceneBaseDataset: dataset_type %r is not supported (blender, llff and nsvf are)' % (cfg.dataset_type,))
         H, W, focal = hwf
         H, W = int(H), int(W)
         if K is None:
@@ -585,3 +623,6 @@ class PassIterHook:
 from . import multiscale  # noqa: E402,F401  (registers MipMultiScaleSample and MipMultiScaleDataset: the data side of mipnerf_multiscale.py)
 from . import bodydata  # noqa: E402,F401  (registers NeuralBodyDataset, AniNeRFDataset and their seven transforms: the data side of nb_zjumocap_*.py / an_*.py)
 from . import genebody  # noqa: E402,F401  (registers GeneBodyDataset: the data side of gnr_genebody.py)
+from . import bungeedata  # noqa: E402,F401  (registers BungeeDataset and its three transforms: the data side of bungeenerf_multiscale_google.py)
+from . import kilodata  # noqa: E402,F401  (registers KiloNerfDataset, KiloNerfNodeDataset and ExampleSample: the data side of kilonerf_*.py)
+from . import hashdata  # noqa: E402,F401  (registers HashNerfDataset and the four instant-ngp transforms: the data side of configs/instant_ngp/*.py)
