@@ -317,6 +317,11 @@ BUNGEEDATA_SIGNATURES = {
     'xr_bgd_frame': (_i32, [_vp, _u32, _u32, _f, _f, _f, _f, _u32, _i32, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# KiloNeRF distillation's validation numbers (csrc/xr_kilotree.hip, declared in include/xrnerf_mi355_kilotree.h): a table of its own as well
+KILOTREE_SIGNATURES = {
+    'xr_kilotree_val_metrics': (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _u32, _u32, C.c_int32, _vp, _i32, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -376,7 +381,7 @@ def load():
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
             list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()) + list(GENEBODY_SIGNATURES.items()) + \
-            list(BUNGEEDATA_SIGNATURES.items()):
+            list(BUNGEEDATA_SIGNATURES.items()) + list(KILOTREE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -80,6 +80,9 @@ SOURCES = {
     # BungeeNeRF data (a training item, a validation frame): the training rays are double arithmetic in numpy's operation order, rounded
     # to fp32 once, the frame's rays and every bound and z-value are un-fused fp32 in torch's -- bit for bit their results, nothing fused
     'xr_bungeedata.hip': ['-ffp-contract=off'],
+    # KiloNeRF distillation's validation numbers (error means, quantile and equal-error split selects, saturation): the per-element errors
+    # d d, |d| and |d| / (|t| + 0.1f) are fp32 in torch's operation order and rank the points -- bit for bit its results, nothing fused
+    'xr_kilotree.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

@@ -153,7 +153,12 @@ def load_reference_distilled_checkpoint(path):
     shim = types.ModuleType('xrnerf_amd_pickle_shim')
     shim.Unpickler, shim.load, shim.loads = _Unpickler, pickle.load, pickle.loads
     shim.__dict__.update({k: getattr(pickle, k) for k in ('HIGHEST_PROTOCOL', 'DEFAULT_PROTOCOL', 'PickleError', 'UnpicklingError')})
-    cp = torch.load(path, map_location='cpu', pickle_module=shim, weights_only=False)
+    return tree_to_checkpoint(torch.load(path, map_location='cpu', pickle_module=shim, weights_only=False))
+
+
+def tree_to_checkpoint(cp):
+    """{'root_nodes': [Node, ...]} (the distillation's tree, read back or live: kilo_tree.leaves_to_checkpoint) -> the plain dict
+    KiloNerfMLP reads: leaves in the breadth-first order of kilonerf_mlp.py:53-62, their weights merged into `multimatmul` layout"""
     queue = list(cp['root_nodes'])
     leaves = []
     for node in queue:                                   # the list grows while it is walked, like the reference's

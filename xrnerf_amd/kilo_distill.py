@@ -186,6 +186,20 @@ class StudentMultiNetwork(nn.Module):
         self.alpha_linear = lin(H, 1, 'linear' if yen else 'relu')
         self.rgb_linear = lin(direction_layer_size, 3, 'linear' if yen else 'sigmoid')
 
+        self._single_network_args = (num_position_channels, num_direction_channels, num_output_channels, hidden_layer_size, num_hidden_layers,
+                                     refeed_position_index, late_feed_direction, direction_layer_size, nonlinearity_initalization, False, None,
+                                     alpha_rgb_initalization)
+
+    def get_single_network(self, network_index):
+        """extract_single_network (multi_modules.py:672-710): a one-network copy of network `network_index` on the host, what the
+        distillation's tree keeps per fitted node ('bmm' layout [1, out, in]; kilo.tree_to_checkpoint reads it)"""
+        with torch.random.fork_rng(devices=[]):          # the copy's own initial draw must not move the caller's stream
+            single = StudentMultiNetwork(1, *self._single_network_args)
+        with torch.no_grad():
+            for dst, src in zip(single.parameters(), self.parameters()):
+                dst.copy_(src[network_index:network_index + 1])
+        return single
+
     def ordered_parameters(self):
         """(weight, bias) per layer in the packed block order, weights transposed to the kernels' [N, in, out]"""
         layers = list(self.pts_linears) + [self.alpha_linear, self.feature_linear, self.direction_layer, self.rgb_linear]
@@ -238,6 +252,10 @@ class KiloNerfMultiNetwork(nn.Module):
     @property
     def arch(self):
         return self.embedder.multires, self.embedder.multires_dirs, self.multi_network.num_hidden_layers
+
+    def get_single_network(self, network_index):
+        """kilonerf_multinet.py:99-102"""
+        return self.multi_network.get_single_network(network_index)
 
     def forward(self, data):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -3227,3 +3227,58 @@ def bgd_frame(c2w, H, W, K, S=0, ray_nearfar='sphere', scene_origin=(0., 0., 0.)
                                            mode, C.cast(gc, C.c_void_p), r2_top, r2_earth, s, *[_ptr(out.get(k)) for k in BGD_FRAME_OUTPUTS], _stream()),
                    'xr_bgd_frame')
     return out
+
+
+# ------------------------------------------------------------------ KiloNeRF distillation's validation numbers (xrnerf_mi355_kilotree.h)
+KILOTREE_COLS = 16                       # XR_KILOTREE_COLS
+KILOTREE_MAX_POINTS = 1 << 24            # XR_KILOTREE_MAX_POINTS
+KT_MSE, KT_MAE, KT_MAPE, KT_QUANTILE, KT_SATURATION, KT_THRESHOLD, KT_METRIC_MAX = 0, 3, 6, 9, 12, 13, 14
+KILOTREE_METRICS = {'mse': 0, 'mae': 1, 'mape': 2}
+
+
+def kilotree_kernels_available():
+    """the loaded library handle has xr_kilotree.hip's entry point (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_kilotree_val_metrics')
+
+
+def _kt_rows(t, cols, N, P, what):
+    """(data pointer, network stride, row stride) of an [N, P, cols] fp32 device view whose rows are contiguous: no copy is made of a
+    column slice of wider example rows"""
+    if not _on_device(t):
+        raise _lib.XrError('xrnerf_amd ops need ROCm device tensors (got a %s tensor): there is no CPU fallback' % t.device)
+    if t.dtype != torch.float32 or tuple(t.shape) != (N, P, cols):
+        raise _lib.XrError('kilo_val_metrics: %s [%d, %d, %d] fp32 (got %s %r)' % (what, N, P, cols, t.dtype, tuple(t.shape)))
+    if t.stride(2) != 1 or t.stride(1) < 0 or t.stride(0) < 0:
+        t = t.contiguous()
+    return t, C.c_void_p(t.data_ptr()), int(t.stride(0)), int(t.stride(1))
+
+
+def kilo_val_metrics(out, targets, quantile_index, points=None, split_axis=None, split_metric='mse', want_point_metric=False):
+    """one validation pass of N student networks -> (table [N, KILOTREE_COLS] fp32 on the device, point_metric [N, P] or None).
+    out [N,P,4]; targets [N,P,4] and points [N,P,3] may be column slices of the example rows.  split_axis: [N] int32 device tensor (or a
+    list of ints), -1 = no split wanted for that network.  The columns (KT_*) and their arithmetic are xrnerf_mi355_kilotree.h's.
+    quantile_index outside [0, P) is refused (-22).  Nothing is read back."""
+    if out.dim() != 3 or out.shape[2] != 4 or out.dtype != torch.float32:
+        raise _lib.XrError('kilo_val_metrics: out [N, P, 4] fp32 (got %s %r)' % (out.dtype, tuple(out.shape)))
+    if split_metric not in KILOTREE_METRICS:
+        raise _lib.XrError('kilo_val_metrics: split_metric is one of %r (got %r)' % (sorted(KILOTREE_METRICS), split_metric))
+    N, P = int(out.shape[0]), int(out.shape[1])
+    if not out.is_contiguous() or out.data_ptr() % 16:
+        out = out.contiguous().clone() if out.data_ptr() % 16 else out.contiguous()
+    targets, pt, t_net, t_row = _kt_rows(targets, 4, N, P, 'targets')
+    pp, p_net, p_row = None, 0, 0
+    axis = None
+    if split_axis is not None:
+        if points is None:
+            raise _lib.XrError('kilo_val_metrics: split_axis needs points')
+        points, pp, p_net, p_row = _kt_rows(points, 3, N, P, 'points')
+        axis = split_axis if torch.is_tensor(split_axis) else torch.tensor([int(v) for v in split_axis], dtype=torch.int32)
+        axis = axis.to(device=out.device, dtype=torch.int32).contiguous()
+        if tuple(axis.shape) != (N,):
+            raise _lib.XrError('kilo_val_metrics: split_axis [%d] (got %r)' % (N, tuple(axis.shape)))
+    table = torch.empty((N, KILOTREE_COLS), dtype=torch.float32, device=out.device)
+    pm = torch.empty((N, P), dtype=torch.float32, device=out.device) if want_point_metric else None
+    with _span('xr_kilotree_val_metrics', N * P, train=False):
+        _lib.check(_lib.load().xr_kilotree_val_metrics(_ptr(out), pt, t_net, t_row, pp, p_net, p_row, N, P, int(quantile_index), _ptr(axis),
+                                                       KILOTREE_METRICS[split_metric], _ptr(table), _ptr(pm), _stream()), 'xr_kilotree_val_metrics')
+    return table, pm
