@@ -322,6 +322,13 @@ KILOTREE_SIGNATURES = {
     'xr_kilotree_val_metrics': (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _u32, _u32, C.c_int32, _vp, _i32, _vp, _vp, _vp]),
 }
 
+# The optimiser step over a work list and the log window (csrc/xr_optim.hip, declared in include/xrnerf_mi355_optim.h): a table of its own as well
+OPTIM_SIGNATURES = {
+    'xr_adam_step_list': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f, _f, _f, _f, _f, _f, _f, _vp]),
+    'xr_adam_list_capacity': (_i32, []),
+    'xr_log_window_add': (_i32, [_i32, _vp, _u32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -381,7 +388,7 @@ def load():
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
             list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()) + list(GENEBODY_SIGNATURES.items()) + \
-            list(BUNGEEDATA_SIGNATURES.items()) + list(KILOTREE_SIGNATURES.items()):
+            list(BUNGEEDATA_SIGNATURES.items()) + list(KILOTREE_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

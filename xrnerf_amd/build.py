@@ -83,6 +83,9 @@ SOURCES = {
     # KiloNeRF distillation's validation numbers (error means, quantile and equal-error split selects, saturation): the per-element errors
     # d d, |d| and |d| / (|t| + 0.1f) are fp32 in torch's operation order and rank the points -- bit for bit its results, nothing fused
     'xr_kilotree.hip': ['-ffp-contract=off'],
+    # the optimiser step over a work list and the log window: adam1 / ema1 un-fused exactly as xr_misc.hip compiles them, so a tensor updated
+    # by the list kernel is bit for bit what xr_adam_step_multi makes of it
+    'xr_optim.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

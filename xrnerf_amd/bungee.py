@@ -483,13 +483,7 @@ def train_iteration(net, batch, optimizer, rands=None):
     Each stage gets a shallow copy of the batch (the reference hands every stage the same dict, which train_step mutates: its second
     stage would see the first stage's fine z_vals and fail on the 'samples' tuple).  rands: per-stage resampling draws, or None.
     -> the per-stage train_step outputs."""
-    outs = []
-    for stage in range(int(torch.max(batch['scale_code'])) + 1):
-        o = net.train_step(dict(batch), optimizer, stage=stage, rand=None if rands is None else rands[stage])
-        outs.append(o)
-        if o['log_vars']['loss'] == 0.:
-            continue
-        optimizer.zero_grad()
-        o['loss'].backward()
-        optimizer.step()
-    return outs
+    from . import runner as _runner
+    r = _runner.IterRunner(net, optimizer)
+    r.register_hook(_runner.OptimizerHook(), 'ABOVE_NORMAL')
+    return _runner.bungee_stages(r, batch, rands=rands)

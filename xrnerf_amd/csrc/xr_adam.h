@@ -20,3 +20,14 @@ __device__ inline float ema1(float e, float p, float mom) { return (1.f - mom) *
 // what a kernel needs to apply the update itself: the whole tensor's p / m / v / ema (ema nullable) + the step's constants
 // (step_size = lr / (1 - beta1^t), bc2s = sqrt(1 - beta2^t), as xr_adam_step_multi passes them to its kernel)
 struct XrAdamArgs { float* p; float* m; float* v; float* ema; float b1, b2, step_size, bc2s, eps, wd, mom, gs; };
+
+// the optimiser kernels' 16-byte accesses (k_adam_multi of xr_misc.hip, k_adam_list of xr_optim.hip), NT = non-temporal: one definition
+typedef float am_f4 __attribute__((ext_vector_type(4)));
+template <bool NT> __device__ __forceinline__ float4 am_ld(const float* p, size_t i) {
+    if (NT) { const am_f4 r = __builtin_nontemporal_load(reinterpret_cast<const am_f4*>(p) + i); return make_float4(r.x, r.y, r.z, r.w); }
+    return reinterpret_cast<const float4*>(p)[i];
+}
+template <bool NT> __device__ __forceinline__ void am_st(float* p, size_t i, const float4 v) {
+    if (NT) { am_f4 r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; __builtin_nontemporal_store(r, reinterpret_cast<am_f4*>(p) + i); }
+    else reinterpret_cast<float4*>(p)[i] = v;
+}

@@ -141,15 +141,7 @@ struct AdamTensors { float* p[4]; const float* g[4]; float* m[4]; float* v[4]; f
 // step -- go through non-temporal loads / stores so that the parameters, which the next step's gather reads right away, are
 // what the caches keep (build with -DXR_ADAM_NT=0 to switch it off -- tools/build_variant.sh; measured in the training loop, profiles/r03_adam_nontemporal.txt:
 // 0.534 -> 0.520 ms per step: the gather 93 -> 89 us, the scatter 113 -> 108 us, this launch 71 -> 70 us)
-typedef float am_f4 __attribute__((ext_vector_type(4)));
-template <bool NT> __device__ __forceinline__ float4 am_ld(const float* p, size_t i) {
-    if (NT) { const am_f4 r = __builtin_nontemporal_load(reinterpret_cast<const am_f4*>(p) + i); return make_float4(r.x, r.y, r.z, r.w); }
-    return reinterpret_cast<const float4*>(p)[i];
-}
-template <bool NT> __device__ __forceinline__ void am_st(float* p, size_t i, const float4 v) {
-    if (NT) { am_f4 r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; __builtin_nontemporal_store(r, reinterpret_cast<am_f4*>(p) + i); }
-    else reinterpret_cast<float4*>(p)[i] = v;
-}
+// (am_ld / am_st: xr_adam.h, shared with the list kernel of xr_optim.hip)
 template <bool NT>
 __global__ __launch_bounds__(256) void k_adam_multi(AdamTensors t, int nt, float b1, float b2, float step_size, float bc2s,
                                                      float eps, float wd, float mom, float gs) {

@@ -302,3 +302,96 @@ def evaluate_frames(render, poses, gts, white_bkgd_mask=True):
         out['average_' + k] = sum(out[k]) / n
     out['log'] = 'On testset, mse is {:.5f}, psnr is {:.5f}, ssim is {:.5f}'.format(out['average_mse'], out['average_psnr'], out['average_ssim'])
     return out
+
+
+# ------------------------------------------------------------------------------------------ the spiral hooks
+def imageio_module():
+    """imageio where it is installed (a module that can write a clip), else None"""
+    try:
+        import imageio
+    except ImportError:
+        return None
+    return imageio if hasattr(imageio, 'mimwrite') else None
+
+
+def write_frames(folder, name, frames8, fps=30):
+    """the frames of one clip: PNGs folder/<name>/000.png ..., and folder/<name>.mp4 as the reference writes it (imageio.mimwrite,
+    quality 8) only where imageio imports"""
+    clip = os.path.join(folder, name)
+    os.makedirs(clip, exist_ok=True)
+    for i, f in enumerate(frames8):
+        _save_png(os.path.join(clip, '{:03d}.png'.format(i)), f if f.ndim == 3 else f[..., None])
+    imageio = imageio_module()
+    if imageio is None:
+        return False
+    imageio.mimwrite(clip + '.mp4', frames8, fps=fps, quality=8)
+    return True
+
+
+class SaveSpiralHook:
+    """core/hooks/validation_hooks.py:24-51: the spiral frames of a validation, work_dir/save_folder/<iter>_rgb and <iter>_disp
+    (to8b(rgb), to8b(disp / max disp))"""
+
+    def __init__(self, save_folder='validation'):
+        self.save_folder = save_folder
+
+    def after_val_iter(self, runner):
+        cur_iter = runner.iter
+        spiral_rgbs = np.stack(runner.outputs['spiral_rgbs'], 0)
+        spiral_disps = np.stack(runner.outputs['spiral_disps'], 0)
+        spiral_dir = os.path.join(runner.work_dir, self.save_folder)
+        os.makedirs(spiral_dir, exist_ok=True)
+        write_frames(spiral_dir, '{}_rgb'.format(cur_iter), to8b(spiral_rgbs), fps=30)
+        write_frames(spiral_dir, '{}_disp'.format(cur_iter), to8b(spiral_disps / np.max(spiral_disps)), fps=30)
+
+
+class NBSaveSpiralHook:
+    """core/hooks/validation_hooks.py:54-92: the first frame of every test item, collected over the epoch, as work_dir/save_folder/rgb
+    and disp; the epoch counter moves on here (a ('val', 1) workflow never advances it)"""
+
+    def __init__(self, save_folder='validation'):
+        self.save_folder = save_folder
+        self.rgbs, self.disps = [], []
+
+    def after_val_iter(self, runner):
+        self.rgbs.append(runner.outputs['rgbs'][0])
+        self.disps.append(runner.outputs['disps'][0])
+
+    def after_val_epoch(self, runner):
+        spiral_dir = os.path.join(runner.work_dir, self.save_folder)
+        os.makedirs(spiral_dir, exist_ok=True)
+        spiral_rgbs, spiral_disps = np.array(self.rgbs), np.array(self.disps)
+        write_frames(spiral_dir, 'rgb', to8b(spiral_rgbs), fps=30)
+        write_frames(spiral_dir, 'disp', to8b(spiral_disps / np.max(spiral_disps)), fps=30)
+        runner._epoch += 1
+
+
+class HashSaveSpiralHook:
+    """core/hooks/hash_hook.py:45-103: the instant-ngp test frames sorted by idx, white where alpha < 0.99, as
+    work_dir/save_folder/<prefix>_rgb and <prefix>_alpha (prefix: the checkpoint's iteration, or 'latest')"""
+
+    def __init__(self, save_folder='validation', cfg=None):
+        self.save_folder = save_folder
+        self.prefix = cfg.load_from.split('/')[-1].split('.')[-2].replace('iter_', '')
+        self.prefix = 'latest' if len(self.prefix) == 0 else self.prefix
+
+    def before_val_epoch(self, runner):
+        self.spiral_data = []
+
+    def after_val_iter(self, runner):
+        self.spiral_data.append([runner.outputs['idx'], runner.outputs['spiral_rgb'], runner.outputs['spiral_alpha']])
+
+    def after_val_epoch(self, runner):
+        spiral_dir = os.path.join(runner.work_dir, self.save_folder)
+        os.makedirs(spiral_dir, exist_ok=True)
+        self.spiral_data = self.apply_mask(sorted(self.spiral_data, key=lambda x: x[0]))
+        write_frames(spiral_dir, '{}_rgb'.format(self.prefix), to8b(np.stack([x[1] for x in self.spiral_data], 0)), fps=25)
+        write_frames(spiral_dir, '{}_alpha'.format(self.prefix), to8b(np.stack([x[2] for x in self.spiral_data], 0)), fps=25)
+        runner._epoch += 1
+
+    def apply_mask(self, spiral_data):
+        for i in range(len(spiral_data)):
+            alpha, rgb = spiral_data[i][2], spiral_data[i][1]
+            mask = (alpha >= 0.99).astype(np.float64)
+            spiral_data[i][1] = rgb * mask + 1 * (1 - mask)
+        return spiral_data

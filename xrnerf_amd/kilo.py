@@ -337,6 +337,61 @@ class KiloNerfNetwork(NerfNetwork):
         log_vars = {'loss': loss.detach(), 'psnr': psnr.detach(), 'L2 reg': l2_loss.detach()}
         return {'loss': loss, 'log_vars': log_vars, 'num_samples': ret['rgb'].shape[0]}
 
+    def _render_pose(self, pose, gmin, gmax):
+        """one frame through the validation pipeline with the scene's box put back in (the pipeline starts from the pose alone)"""
+        from .networks import recover_shape
+        frame = self.val_pipeline({'pose': pose})
+        frame['global_domain_min'], frame['global_domain_max'] = gmin, gmax
+        ret = self.batchify_forward(frame, is_test=True)
+        return ret, frame['src_shape'], recover_shape
+
+    def val_step(self, data, optimizer=None, **kwargs):
+        """networks/kilonerf.py:61-115: NerfNetwork.val_step with the scene's box handed to every frame; rank 0 only"""
+        import time
+        from .networks import get_dist_info, unfold_batching
+        if self.phase == 'test':
+            return self.test_step(data, **kwargs)
+        rank, _ = get_dist_info()
+        if rank != 0:
+            return {}
+        for k in data:
+            data[k] = unfold_batching(data[k])
+        poses, images, spiral_poses = data['poses'], data['images'], data['spiral_poses']
+        gmin, gmax = data['global_domain_min'], data['global_domain_max']
+        rgbs, disps, gt_imgs, elapsed = [], [], [], []
+        with torch.no_grad():
+            for i in range(poses.shape[0]):
+                start = time.time()
+                ret, shape, recover_shape = self._render_pose(poses[i], gmin, gmax)
+                elapsed_time = time.time() - start          # pipeline and forward, as the reference times it
+                rgbs.append(recover_shape(ret['rgb'], shape).cpu().numpy())
+                disps.append(recover_shape(ret['disp'], shape).cpu().numpy())
+                gt_imgs.append(images[i].cpu().numpy())
+                elapsed.append(elapsed_time)
+            spiral_rgbs, spiral_disps = [], []
+            for i in range(spiral_poses.shape[0]):
+                ret, shape, recover_shape = self._render_pose(spiral_poses[i], gmin, gmax)
+                spiral_rgbs.append(recover_shape(ret['rgb'], shape).cpu().numpy())
+                spiral_disps.append(recover_shape(ret['disp'], shape).cpu().numpy())
+        return {'spiral_rgbs': spiral_rgbs, 'spiral_disps': spiral_disps, 'rgbs': rgbs, 'disps': disps, 'gt_imgs': gt_imgs,
+                'elapsed_time': elapsed}
+
+    def test_step(self, data, **kwargs):
+        """networks/kilonerf.py:117-144 (val_step + phase == 'test'); 'idx' is carried along when the item has one (TestHook reads it)"""
+        from .networks import get_dist_info, unfold_batching
+        rank, _ = get_dist_info()
+        if rank != 0:
+            return {}
+        for k in data:
+            data[k] = unfold_batching(data[k])
+        image = data['image']
+        with torch.no_grad():
+            ret, shape, recover_shape = self._render_pose(data['pose'], data['global_domain_min'], data['global_domain_max'])
+        out = {'rgb': recover_shape(ret['rgb'], shape).cpu().numpy(), 'gt_img': image.cpu().numpy()}
+        if 'idx' in data:
+            out['idx'] = int(data['idx'].item()) if torch.is_tensor(data['idx']) else int(data['idx'])
+        return out
+
 
 # ------------------------------------------------------------------ synthetic Lego-shaped scene (bench / smoke / tests)
 LEGO_RESOLUTION = [144, 256, 160]             # configs/kilonerf/kilonerf_finetune_Synthetic_NeRF_base01.py:18

@@ -505,3 +505,30 @@ def distill(teacher_mlp, global_domain_min, global_domain_max, fixed_resolution,
         sd[nm + '.weight'], sd[nm + '.bias'] = tensors[2 * i].detach().cpu().contiguous(), tensors[2 * i + 1].detach().cpu().contiguous()
     return {'domain_mins': dmins_all, 'domain_maxs': dmaxs_all, 'state_dict': sd, 'num_hidden_layers': num_hidden_layers,
             'error_metrics': metrics}
+
+
+class BuildOccupancyTreeHook:
+    """core/hooks/build_occupancy_tree_hook.py:18-123: after the pretraining run, the occupancy grid of the trained coarse MLP
+    (build_occupancy_grid over cfg.build_occupancy_tree_config) saved as <occupancy work_dir>/occupancy.pth -- the file the fine-tuning
+    config's mlp loads"""
+
+    def __init__(self, cfg=None):
+        assert cfg, 'cfg not input in BuildOccupancyTreeHook'
+        self.cfg = cfg
+        self.occupancy_config = cfg.build_occupancy_tree_config
+
+    def after_run(self, runner):
+        import os
+        from .kilodata import get_global_domain_min_and_max
+        oc = self.occupancy_config
+        pretrained_nerf = getattr(runner.model, 'module', runner.model).mlp
+        gmin, gmax = get_global_domain_min_and_max(self.cfg, torch.device('cpu'))
+        occupancy_grid = build_occupancy_grid(pretrained_nerf, gmin.tolist(), gmax.tolist(), list(oc.resolution), tuple(oc.subsample_resolution),
+                                              oc.threshold, oc.voxel_batch_size)
+        occupied = int(occupancy_grid.sum().item())
+        runner.logger.info('{} out of {} voxels are occupied. {:.2f}%'.format(occupied, occupancy_grid.numel(),
+                                                                           100 * occupied / occupancy_grid.numel()))
+        os.makedirs(oc.work_dir, exist_ok=True)
+        occupancy_filename = oc.work_dir + '/occupancy.pth'
+        torch.save(occupancy_grid, occupancy_filename)
+        runner.logger.info('Saved occupancy grid to {}'.format(occupancy_filename))

@@ -3282,3 +3282,52 @@ def kilo_val_metrics(out, targets, quantile_index, points=None, split_axis=None,
         _lib.check(_lib.load().xr_kilotree_val_metrics(_ptr(out), pt, t_net, t_row, pp, p_net, p_row, N, P, int(quantile_index), _ptr(axis),
                                                        KILOTREE_METRICS[split_metric], _ptr(table), _ptr(pm), _stream()), 'xr_kilotree_val_metrics')
     return table, pm
+
+
+# ------------------------------------------------------------------ the optimiser step over a work list, the log window (xrnerf_mi355_optim.h)
+LOG_WINDOW_SLOTS = 16                    # XR_LOG_WINDOW_SLOTS
+
+
+def optim_kernels_available():
+    """the loaded library handle has xr_optim.hip's entry points (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_adam_step_list')
+
+
+def adam_list_capacity():
+    """tensors per launch of adam_step_list (XR_ADAM_LIST_CAPACITY)"""
+    return int(_lib.load().xr_adam_list_capacity())
+
+
+def adam_step_list(ps, gs, ms, vs, step, lr=1e-2, beta1=0.9, beta2=0.99, eps=1e-15, weight_decay=1e-6, emas=None, ema_momentum=0.05,
+                   grad_scale=1.0):
+    """adam_step_multi's update for ANY number of tensors that share `step` and the constants: one launch per adam_list_capacity() tensors,
+    small tensors sharing workgroups.  A tensor that is not 16-byte aligned (a view at an odd offset) is updated by 4-byte accesses."""
+    k = len(ps)
+    arr = lambda ts: (C.c_void_p * k)(*[t.data_ptr() if t is not None else None for t in ts])
+    for t in list(ps) + list(gs) + list(ms) + list(vs) + [e for e in (emas or ()) if e is not None]:
+        _ptr(t)     # validates device / contiguity
+        if t.dtype != torch.float32:
+            raise _lib.XrError('adam_step_list takes float32 tensors (got %s)' % t.dtype)
+    ns = (C.c_size_t * k)(*[p.numel() for p in ps])
+    with _span('xr_adam_step', sum(p.numel() for p in ps)):
+        _lib.check(_lib.load().xr_adam_step_list(k, arr(ps), arr(gs), arr(ms), arr(vs), arr(emas) if emas else None, ns, int(step), lr, beta1,
+                                                 beta2, eps, weight_decay, ema_momentum, float(grad_scale), _stream()), 'xr_adam_step_list')
+
+
+def log_window_add(values, num_samples, window, first_slot=0):
+    """window [2 * LOG_WINDOW_SLOTS] float64 on the device: window[s] += values[i] * num_samples, window[LOG_WINDOW_SLOTS + s] += num_samples,
+    s = first_slot + i, for the one-element fp32 device tensors `values` (first_slot + len(values) <= LOG_WINDOW_SLOTS), one launch, nothing
+    read back"""
+    k = len(values)
+    if not (0 <= first_slot and 1 <= k and first_slot + k <= LOG_WINDOW_SLOTS):
+        raise _lib.XrError('log_window_add: slots %d .. %d of %d' % (first_slot, first_slot + k - 1, LOG_WINDOW_SLOTS))
+    for t in values:
+        _ptr(t)
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise _lib.XrError('log_window_add takes one-element float32 tensors (got %s %r)' % (t.dtype, tuple(t.shape)))
+    if window.dtype != torch.float64 or window.numel() != 2 * LOG_WINDOW_SLOTS:
+        raise _lib.XrError('log_window_add: window is [%d] float64' % (2 * LOG_WINDOW_SLOTS))
+    arr = (C.c_void_p * max(k, 1))(*[t.data_ptr() for t in values])
+    _ptr(window)
+    _lib.check(_lib.load().xr_log_window_add(k, arr, int(num_samples), C.c_void_p(window.data_ptr() + 8 * first_slot), _stream()),
+               'xr_log_window_add')

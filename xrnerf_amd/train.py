@@ -99,6 +99,20 @@ class FusedAdam(torch.optim.Optimizer):
                 st = self._state(p, group)
                 st['step'] += 1
                 todo.append((p, p.grad if p.grad.is_contiguous() else p.grad.contiguous(), st))
+            if todo and all(ops._on_device(t[0]) for t in todo) and ops.optim_kernels_available():
+                # the list kernel (xr_adam_step_list): tensors that share a step count go out as one work list, however many they are --
+                # the same bits as the launches below, tensor by tensor
+                by_step = {}
+                for t in todo:
+                    by_step.setdefault(t[2]['step'], []).append(t)
+                for step, chunk in by_step.items():
+                    emas = [c[2].get('ema') for c in chunk] if group['ema_momentum'] is not None else None
+                    mom = self._ema_momentum(group, step) if emas else 0.0
+                    ops.adam_step_list([c[0] for c in chunk], [c[1] for c in chunk], [c[2]['m'] for c in chunk], [c[2]['v'] for c in chunk],
+                                       step, group['lr'], group['betas'][0], group['betas'][1], group['eps'], group['weight_decay'], emas,
+                                       mom, grad_scale=grad_scale)
+                continue
+            # host tensors (refused by the entry point) and a library without the list kernel: the launches of up to 4 tensors.
             # tensors that share a step count go out in one launch (up to 4 per launch)
             while todo:
                 chunk = [t for t in todo[:4] if t[2]['step'] == todo[0][2]['step']]
