@@ -329,6 +329,13 @@ OPTIM_SIGNATURES = {
     'xr_log_window_add': (_i32, [_i32, _vp, _u32, _vp, _vp]),
 }
 
+# The instant-ngp loop's per-iteration log sums and the logged loop (csrc/xr_ngprun.hip, xr_step.hip, declared in
+# include/xrnerf_mi355_ngprun.h): a table of its own as well
+NGPRUN_SIGNATURES = {
+    'xr_ngp_log_add': (_i32, [_vp, _u32, _vp, _u32, _u32, _vp]),
+    'xr_ngp_loop_run_logged': (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _u32, C.c_char_p, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -388,7 +395,7 @@ def load():
             list(ANINERF_SIGNATURES.items()) + list(NEURALBODY_SIGNATURES.items()) + list(GNR_SIGNATURES.items()) + list(GNR_RENDER_SIGNATURES.items()) + \
             list(GNR_ENCODER_SIGNATURES.items()) + list(GNR_RECON_SIGNATURES.items()) + list(GNR_RASTER_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
             list(PIPELINE_SIGNATURES.items()) + list(MULTISCALE_SIGNATURES.items()) + list(BODYDATA_SIGNATURES.items()) + list(GENEBODY_SIGNATURES.items()) + \
-            list(BUNGEEDATA_SIGNATURES.items()) + list(KILOTREE_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+            list(BUNGEEDATA_SIGNATURES.items()) + list(KILOTREE_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(NGPRUN_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -5,8 +5,10 @@
 The config is the reference's Python file, loaded as it is (load_config: runpy + `_base_`); datasets, network, optimiser, runner and hooks
 are built from the names it gives.  The loaders are in-process (runner.DataLoader over pipelines.iterate), the optimiser is train.FusedAdam
 where the parameters live on the GPU, the runners and the lr / optimizer / checkpoint / log hooks are xrnerf_amd.runner's.
-Out of scope, each refused by name: distributed runs, the instant-ngp config (train.Trainer and the native loop are its path),
-gradient clipping, logger hooks other than TextLoggerHook, custom_hooks.
+The instant-ngp config (a HashNerfNetwork on HashNerfDataset data) trains through runner.NgpIterRunner, which drives train.Trainer's native
+loop in spans between the iterations at which a hook is due.
+Out of scope, each refused by name: distributed runs, gradient clipping, logger hooks other than TextLoggerHook, custom_hooks other than the
+instant-ngp config's EMAHook.
 """
 import argparse
 import logging
@@ -113,9 +115,17 @@ def _device(cfg):
 def _refuse(cfg):
     if cfg.get('distributed', False):
         raise NotImplementedError('distributed=True: xrnerf_amd.apis runs a single process (multi-GPU training: xrnerf_amd.dist)')
-    if cfg.get('method') == 'instant_ngp' or cfg.model.get('type') == 'HashNerfNetwork':
-        raise NotImplementedError('the instant-ngp config (HashNerfNetwork) does not run through this runner: '
-                                  'xrnerf_amd.train.Trainer and the native loop are its path')
+    if _is_ngp(cfg):
+        missing = [k for k in ('sampler', 'mlp', 'render') if k not in cfg.model]
+        data_type = cfg.get('data', {}).get('train', {}).get('type')
+        if missing or data_type != 'HashNerfDataset':
+            raise NotImplementedError('a HashNerfNetwork runs as the instant-ngp config only (sampler, mlp and render in the model dict, '
+                                      'HashNerfDataset data): %s' % ('the model dict has no %s' % ', '.join(missing) if missing else
+                                                                     'data.train is a %r' % (data_type,)))
+
+
+def _is_ngp(cfg):
+    return (cfg.get('model', None) or {}).get('type') == 'HashNerfNetwork'
 
 
 def build_dataloader(cfg, mode='train'):
@@ -137,20 +147,30 @@ def get_optimizer(model, cfg):
         params, opt = model.get_params(), {'lr': opt['lr']}
     else:
         params = [p for p in model.parameters() if p.requires_grad]
+    if _is_ngp(cfg):
+        # the three NGP tensors (the direction encoding has none) in train.FusedAdam, whose fused EMA state is what the config's EMAHook keeps
+        params = [p for p in params if p.numel() > 0]
+        ema = [h for h in cfg.get('custom_hooks', None) or [] if h.get('type') == 'EMAHook']
+        if ema:
+            from .ngp_hooks import EMAHook
+            hook = EMAHook(**{k: v for k, v in ema[0].items() if k not in ('type', 'priority')})
+            ema_kw = dict(ema_momentum=hook.momentum, ema_warm_up=hook.warm_up)
     if opt.pop('amsgrad', False):
         raise NotImplementedError('optimizer amsgrad=True')
     kw = dict(lr=opt.pop('lr', 1e-3), betas=tuple(opt.pop('betas', (0.9, 0.999))), eps=opt.pop('eps', 1e-8), weight_decay=opt.pop('weight_decay', 0))
     if opt:
         raise NotImplementedError('optimizer keys %r' % sorted(opt))
+    if _is_ngp(cfg):
+        return FusedAdam(params, **dict(kw, **(ema_kw if ema else {})))
     if params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
         return FusedAdam(params, **kw)
     return torch.optim.Adam(params, **kw)
 
 
 def _hook_classes():
-    from . import evaluate, kilo_distill, kilo_tree
-    mods = (pipelines, evaluate, kilo_tree, kilo_distill, _runner)
-    names = ('SetValPipelineHook', 'PassIterHook', 'ValidateHook', 'CalElapsedTimeHook', 'TestHook', 'SaveSpiralHook', 'NBSaveSpiralHook',
+    from . import evaluate, kilo_distill, kilo_tree, ngp_hooks
+    mods = (pipelines, evaluate, kilo_tree, kilo_distill, _runner, ngp_hooks)
+    names = ('PassDatasetHook', 'PassSamplerIterHook', 'ModifyBatchsizeHook', 'EMAHook', 'SetValPipelineHook', 'PassIterHook', 'ValidateHook', 'CalElapsedTimeHook', 'TestHook', 'SaveSpiralHook', 'NBSaveSpiralHook',
              'HashSaveSpiralHook', 'OccupationHook', 'SaveDistillResultsHook', 'DistllCycleHook', 'BuildOccupancyTreeHook', 'MipLrUpdaterHook')
     return {n: next(getattr(m, n) for m in mods if hasattr(m, n)) for n in names}
 
@@ -188,8 +208,12 @@ def train_nerf(cfg):
     network = builder.build_network(cfg.model).to(_device(cfg))
     optimizer = get_optimizer(network, cfg)
     Runner = get_runner(cfg.train_runner)
+    extra = {}
+    if _is_ngp(cfg):
+        # the config still says NerfTrainRunner: the instant-ngp model trains through the span runner over the native loop
+        Runner, extra = _runner.NgpIterRunner, dict(trainset=trainset)
     runner = Runner(network, optimizer=optimizer, work_dir=cfg.work_dir, logger=get_root_logger(log_level=cfg.get('log_level', 'INFO')),
-                    meta=None)
+                    meta=None, **extra)
     runner.timestamp = cfg.get('timestamp', None)
     runner.register_training_hooks(cfg.lr_config, cfg.optimizer_config, cfg.checkpoint_config, cfg.log_config,
                                    custom_hooks_config=cfg.get('custom_hooks', None))

@@ -86,6 +86,9 @@ SOURCES = {
     # the optimiser step over a work list and the log window: adam1 / ema1 un-fused exactly as xr_misc.hip compiles them, so a tensor updated
     # by the list kernel is bit for bit what xr_adam_step_multi makes of it
     'xr_optim.hip': ['-ffp-contract=off'],
+    # the instant-ngp loop's per-iteration log sums: double products and sums that the host build of the same source (tests/hip_emu) rounds
+    # alike -- no fused multiply-add
+    'xr_ngprun.hip': ['-ffp-contract=off'],
     'xr_gemm.hip': [],
     # host-side step executor (calls the entry points above in sequence)
     'xr_step.hip': [],

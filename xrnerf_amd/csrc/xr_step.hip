@@ -7,6 +7,7 @@
 // is allocated or synchronised.
 #include "xr_common.h"
 #include "xr_aux.h"
+#include "../../include/xrnerf_mi355_ngprun.h"
 #include <cstdlib>
 #include <initializer_list>
 
@@ -243,9 +244,15 @@ extern "C" int xr_ngp_window_march(const xr_ngp_window* W, uint32_t first_chunk,
 // k iterations of the trainer's steady state as one call (contract: include/xrnerf_mi355.h, xr_ngp_loop_run): iteration `it` steps on
 // the marched batch in chunk it % XR_NGP_WINDOW of the window, with the three updates inside.  One in-order stream, no events: the
 // marches were enqueued before (xr_ngp_window_march; the caller orders `stream` behind them once).
-extern "C" int xr_ngp_loop_run(const xr_ngp_loop_desc* desc, xr_ngp_loop_state* state, uint32_t k, uint32_t n_rays, const float* lr,
-                               const float* ema_momentum, const char* timed_entry, void* const* timing_events, void* const* iter_events) {
+// `log_window` (nullable; include/xrnerf_mi355_ngprun.h, xr_ngp_loop_run_logged): behind each iteration's step one xr_ngp_log_add launch adds that
+// iteration's loss and psnr to the window.  Null: exactly the launches there were before the argument existed.
+static int xr_ngp_loop_body(const xr_ngp_loop_desc* desc, xr_ngp_loop_state* state, uint32_t k, uint32_t n_rays, const float* lr,
+                            const float* ema_momentum, double* log_window, uint32_t slot_loss, uint32_t slot_psnr, const char* timed_entry,
+                            void* const* timing_events, void* const* iter_events) {
     XR_REQUIRE(desc && state && lr && ema_momentum, "null pointer");
+    XR_REQUIRE(!log_window || (((uintptr_t)log_window & 7) == 0 && slot_loss < XR_LOG_WINDOW_SLOTS && slot_psnr < XR_LOG_WINDOW_SLOTS &&
+                               slot_loss != slot_psnr && n_rays < (1u << 29) && desc->step[0].loss_mse && desc->step[1].loss_mse),
+               "log window: 8-byte aligned, two different slots inside it, n_rays below 2^29, both step sets' loss_mse");
     const xr_ngp_loop_desc& D = *desc;
     xr_ngp_loop_state& S = *state;
     const xr_ngp_window& W = D.window;
@@ -317,9 +324,22 @@ extern "C" int xr_ngp_loop_run(const xr_ngp_loop_desc* desc, xr_ngp_loop_state* 
                 if ((rc = X->finish(X->ctx, D.stream)) != XR_OK) return rc;
             }
         }
+        if (log_window && (rc = xr_ngp_log_add(B.loss_mse, n_rays, log_window, slot_loss, slot_psnr, D.stream)) != XR_OK) return rc;
         S.last_step_set = S.step_turn & 1u;
         S.iter = it + 1;
     }
     if (iter_events) XR_HIP(hipEventRecord((hipEvent_t)iter_events[k], stream));
     return XR_OK;
+}
+
+extern "C" int xr_ngp_loop_run(const xr_ngp_loop_desc* desc, xr_ngp_loop_state* state, uint32_t k, uint32_t n_rays, const float* lr,
+                               const float* ema_momentum, const char* timed_entry, void* const* timing_events, void* const* iter_events) {
+    return xr_ngp_loop_body(desc, state, k, n_rays, lr, ema_momentum, nullptr, 0, 0, timed_entry, timing_events, iter_events);
+}
+
+extern "C" int xr_ngp_loop_run_logged(const xr_ngp_loop_desc* desc, xr_ngp_loop_state* state, uint32_t k, uint32_t n_rays, const float* lr,
+                                      const float* ema_momentum, double* log_window, uint32_t slot_loss, uint32_t slot_psnr,
+                                      const char* timed_entry, void* const* timing_events, void* const* iter_events) {
+    return xr_ngp_loop_body(desc, state, k, n_rays, lr, ema_momentum, log_window, slot_loss, slot_psnr, timed_entry,
+                    timing_events, iter_events);
 }

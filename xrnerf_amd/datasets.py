@@ -107,6 +107,7 @@ class DeviceRayTable:
         self.cur_i = 0
         self.N_rand = 4096
         self.batches_drawn = 0
+        self.iter_n = 0
 
     def get_alldata(self):                  # hashnerf_dataset.py:55-73
         aabb_scale = self.aabb_scale
@@ -120,6 +121,9 @@ class DeviceRayTable:
 
     def set_batchsize(self, bs):            # ModifyBatchsizeHook (core/hooks/hash_hook.py:33-42)
         self.N_rand = int(bs)
+
+    def set_iter(self, iter_n):             # PassIterHook (core/hooks/train_hooks.py:12-23)
+        self.iter_n = iter_n
 
     def next_batch(self, out=None):
         """HashBatchSample + RandomBGColor (pipelines/create.py:153-191, augment.py:290-317), on device, one launch.
@@ -138,7 +142,13 @@ class HashNerfDataset(DeviceRayTable):
 
     cfg keys (configs/instant_ngp/nerf_blender_local01.py:129-160): datadir, half_res, testskip, white_bkgd,
     load_alpha, N_rand_per_sampler, mode ('train' | 'val' | 'test'), val_n.  Image order = (val, train) like
-    hashnerf_dataset.py:33-35; poses -> NGP space with correct_pose [1,-1,-1], scale 0.33, offset 0.5 (:36-40)."""
+    hashnerf_dataset.py:33-35; poses -> NGP space with correct_pose [1,-1,-1], scale 0.33, offset 0.5 (:36-40).
+
+    As a dataset (hashnerf_dataset.py:117-126): `pipeline` is the Compose of the config's list with get_info() as keyword values, as
+    SceneBaseDataset builds it (SetValPipelineHook hands it to the network); an item is next_batch() in 'train' mode, the validation
+    poses and images in 'val' mode and one render pose's rays in 'test' mode, so runner.DataLoader and pipelines.iterate work on it.
+    Training batches are drawn by train.Trainer (next_batch, one launch), not through a loader: the train loader exists for len(), the
+    epoch count and PassIterHook.  In 'test' mode get_alldata() hands the render poses (:65): they are this table's poses."""
 
     def __init__(self, cfg, pipeline=None, device=None, seed=1):
         cfg = dict(cfg)
@@ -169,11 +179,24 @@ class HashNerfDataset(DeviceRayTable):
         else:
             super().__init__(device, poses_ngp, self.images, H, W, focal, seed=seed, shuffle=(self.mode == 'train'))
         self.N_rand = int(cfg.get('N_rand_per_sampler', 4096))
+        self.pipeline = None
+        if pipeline is not None:
+            from .pipelines import Compose
+            datainfo = self.get_info()
+            self.pipeline = Compose([dict(step, **datainfo) if isinstance(step, dict) else step for step in pipeline])
 
     def get_info(self):
         info = super().get_info()
         info.update({'near': self.near, 'far': self.far})
         return info
+
+    def __getitem__(self, idx):             # :117-126
+        if self.mode == 'train':
+            return self.next_batch()
+        if self.mode == 'val':              # the poses on the device: the validation pipeline makes the rays where the pose lives
+            data = self.fetch_val_data()
+            return {'poses': torch.from_numpy(np.ascontiguousarray(data['poses'])).to(self.device), 'images': data['images']}
+        return self.fetch_test_data(idx)
 
     def fetch_val_data(self):               # _fetch_val_data (:99-103): ngp validates on the first val_n images
         return {'poses': self.poses[:self.val_n], 'images': self.images[:self.val_n]}

@@ -3331,3 +3331,25 @@ def log_window_add(values, num_samples, window, first_slot=0):
     _ptr(window)
     _lib.check(_lib.load().xr_log_window_add(k, arr, int(num_samples), C.c_void_p(window.data_ptr() + 8 * first_slot), _stream()),
                'xr_log_window_add')
+
+
+# ------------------------------------------------------------------------------------------ the instant-ngp loop's log sums (xr_ngprun.hip)
+def ngprun_kernels_available():
+    """the loaded library handle has xr_ngprun.hip's entry point (see gnr_kernels_available)"""
+    return hasattr(_lib.load(), 'xr_ngp_log_add')
+
+
+def ngp_log_add(loss_mse, n_rays, window, slot_loss, slot_psnr):
+    """one training iteration's loss and psnr into a log window (LogWindow's layout), one launch, nothing read back:
+    window[slot_loss] += loss_mse[0] * n_rays, window[slot_psnr] += -10 log10(loss_mse[1] / (3 n_rays)) * n_rays (in double), and n_rays
+    into both slots' counts.  loss_mse: the two fp32 scalars of a training step (HashNerfNetwork._last['loss_mse'])."""
+    _ptr(loss_mse)
+    _ptr(window)
+    if loss_mse.dtype != torch.float32 or loss_mse.numel() < 2:
+        raise _lib.XrError('ngp_log_add: loss_mse is the step\'s two float32 scalars (got %s %r)' % (loss_mse.dtype, tuple(loss_mse.shape)))
+    if window.dtype != torch.float64 or window.numel() != 2 * LOG_WINDOW_SLOTS:
+        raise _lib.XrError('ngp_log_add: window is [%d] float64' % (2 * LOG_WINDOW_SLOTS))
+    if not (1 <= int(n_rays) < (1 << 29) and 0 <= int(slot_loss) < LOG_WINDOW_SLOTS and 0 <= int(slot_psnr) < LOG_WINDOW_SLOTS):
+        raise _lib.XrError('ngp_log_add: n_rays is 1 .. 2^29 - 1 and the slots lie inside the window (got %r, %r, %r)' % (n_rays, slot_loss, slot_psnr))
+    _lib.check(_lib.load().xr_ngp_log_add(C.c_void_p(loss_mse.data_ptr()), int(n_rays), C.c_void_p(window.data_ptr()), int(slot_loss),
+                                          int(slot_psnr), _stream()), 'xr_ngp_log_add')

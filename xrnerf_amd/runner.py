@@ -65,6 +65,22 @@ class LogWindow:
                 ops.log_window_add(run, n, self.window, first_slot=start)
                 run = []
 
+    def reserve(self, names, device):
+        """named slots of the device window for a producer that adds to it itself (ops.ngp_log_add, the native instant-ngp loop): the window
+        is made on `device` when there is none yet -> (window tensor, slot of names[0], slot of names[1], ...).  read() serves them like any
+        other name."""
+        device = torch.device(device)
+        if self.window is None:
+            self.window = torch.zeros(2 * ops.LOG_WINDOW_SLOTS, dtype=torch.float64, device=device)
+        elif self.window.device != device:
+            raise ValueError('LogWindow.reserve: the window lives on %s, not on %s' % (self.window.device, device))
+        for k in names:
+            if k not in self.names:
+                if len(self.names) == ops.LOG_WINDOW_SLOTS:
+                    raise ValueError('LogWindow holds %d device scalars (got %r beyond %r)' % (ops.LOG_WINDOW_SLOTS, k, self.names))
+                self.names.append(k)
+        return (self.window,) + tuple(self.names.index(k) for k in names)
+
     def read(self):
         """-> OrderedDict name -> float (the window's weighted average); the window starts again from zero"""
         out = OrderedDict()
@@ -548,6 +564,156 @@ class BungeeNerfTestRunner(EpochRunner):
 def _kilo_distill_runner():
     from .kilo_tree import KiloNerfDistillTrainRunner
     return KiloNerfDistillTrainRunner
+
+
+class _At:
+    """what an LrUpdaterHook's get_lr reads of a runner, at a given iteration"""
+
+    def __init__(self, it, epoch=0):
+        self.iter, self.epoch = it, epoch
+
+
+def _per_iteration_methods(hook):
+    """the per-iteration stages a hook defines (mode-specific or general), by name"""
+    return [n for n in ('before_train_iter', 'after_train_iter', 'before_iter', 'after_iter') if callable(getattr(hook, n, None))]
+
+
+class NgpIterRunner(IterRunner):
+    """The instant-ngp config's training runner: IterRunner whose ('train', n) pairs run as SPANS of the native loop
+    -- one train.Trainer.run(k) per span, i.e. one native call per refresh window with the per-iteration path at the refreshes, exactly as
+    bench.py drives it -- instead of one Python train_step per 0.34-ms iteration.  A span ends at the earliest of the pair's end, max_iters
+    and the next iteration at which a hook is due:
+      absorbed   LrUpdaterHook (-> the trainer's lr_at), OptimizerHook(grad_clip=None), EMAHook, PassSamplerIterHook, ModifyBatchsizeHook
+                 (the trainer does their per-iteration work), PassIterHook and OccupationHook (run at every span's end: the dataset gets
+                 the span's last iteration) -- never end a span
+      interval   CheckpointHook, TextLoggerHook: due where (i + 1) % interval == 0
+      other      a hook with a before_ / after_ _train_iter or _iter method: due every iteration (spans of 1: correct, only slow)
+    At a span's end the due hooks' after_train_iter run in priority order with runner.iter = the span's last iteration.  Every iteration's
+    loss and psnr reach the log window on the device (LogWindow.reserve -> Trainer(log_window=)).  `val` pairs are IterRunner.val.
+    `engine`: anything with run(k) -> the last iteration's outputs and an `iter` attribute (default: a train.Trainer over `trainset`, built
+    behind the before_run hooks)."""
+
+    def __init__(self, model, optimizer=None, work_dir=None, logger=None, meta=None, max_iters=None, max_epochs=None, trainset=None,
+                 engine=None, device=None):
+        super().__init__(model, optimizer=optimizer, work_dir=work_dir, logger=logger, meta=meta, max_iters=max_iters, max_epochs=max_epochs)
+        self.trainset, self.engine, self.device = trainset, engine, device
+        self.lr_at = None
+
+    def register_training_hooks(self, lr_config, optimizer_config=None, checkpoint_config=None, log_config=None, custom_hooks_config=None):
+        """IterRunner's, and custom_hooks=[dict(type='EMAHook', ...)] (mmcv registers custom hooks at their `priority`, NORMAL by default)"""
+        from .ngp_hooks import EMAHook
+        super().register_training_hooks(lr_config, optimizer_config, checkpoint_config, log_config, None)
+        for h in custom_hooks_config or []:
+            h = dict(h)
+            kind = h.pop('type')
+            if kind != 'EMAHook':
+                raise NotImplementedError('custom hook %r: only EMAHook is built' % (kind,))
+            priority = h.pop('priority', 'NORMAL')
+            self.register_hook(EMAHook(**h), priority)
+
+    def resume(self, checkpoint, resume_optimizer=True, map_location='cpu'):
+        super().resume(checkpoint, resume_optimizer=resume_optimizer, map_location=map_location)
+        from .ngp_hooks import EMAHook
+        for h in self._hooks:
+            if isinstance(h, EMAHook) and h.registered:
+                h.alias(self)                  # the optimiser's loaded state tensors are new ones: the buffers name them again
+
+    # -------------------------------------------------------------- planning
+    def _classify(self):
+        from .kilo_tree import OccupationHook
+        from .ngp_hooks import EMAHook, ModifyBatchsizeHook, PassDatasetHook, PassSamplerIterHook
+        from .pipelines import PassIterHook
+        absorbed = (LrUpdaterHook, OptimizerHook, EMAHook, PassSamplerIterHook, ModifyBatchsizeHook)
+        self._span_end, self._interval, self._every = [], [], []
+        for h in self._hooks:
+            if isinstance(h, absorbed):
+                continue
+            if isinstance(h, (PassIterHook, OccupationHook)):
+                self._span_end.append(h)
+            elif isinstance(h, (CheckpointHook, TextLoggerHook)):
+                self._interval.append(h)
+            elif _per_iteration_methods(h):
+                self._every.append(h)
+
+    def _next_due(self, i):
+        """the first iteration >= i at which an interval hook or a per-iteration hook is due (None: never)"""
+        if self._every:
+            return i
+        due = [i + (-(i + 1)) % h.interval for h in self._interval if h.interval and h.interval > 0]
+        return min(due) if due else None
+
+    def _make_engine(self):
+        from .train import Trainer
+        lr_hooks = [h for h in self._hooks if isinstance(h, LrUpdaterHook)]
+        if lr_hooks:
+            hook, base = lr_hooks[0], lr_hooks[0].base_lr[0]
+            self.lr_at = lambda it: float(hook.get_lr(_At(it), base))
+        else:
+            lr = self.optimizer.param_groups[0]['lr']
+            self.lr_at = lambda it: lr
+        if self.engine is None:
+            device = torch.device(self.device) if self.device is not None else next(self.model.parameters()).device
+            self.engine = Trainer(device, dataset=self.trainset, net=self._module(), optimizer=self.optimizer, lr_at=self.lr_at,
+                                  log_window=self.log_buffer.reserve(('loss', 'psnr'), device))
+        self.engine.iter = self.iter               # (a resumed run goes on at its iteration)
+
+    def train_span(self, data_loader, n):
+        """up to `n` training iterations of one ('train', n) workflow pair, as spans"""
+        self.model.train()
+        self.mode = 'train'
+        self.data_loader = data_loader
+        self._epoch = data_loader.epoch
+        end = min(self.iter + n, self._max_iters)
+        while self.iter < end:
+            first = self.iter
+            due = self._next_due(first)
+            last = end - 1 if due is None else min(end - 1, due)
+            k = last - first + 1
+            for h in self._every:                  # (spans of 1: runner.iter is the iteration about to run)
+                fn = getattr(h, 'before_train_iter', None) or getattr(h, 'before_iter', None)
+                if fn is not None:
+                    fn(self)
+            outputs = self.engine.run(k)
+            if not isinstance(outputs, dict):
+                raise TypeError('the engine\'s run() must return a dict')
+            self.outputs = outputs
+            self._iter, self._inner_iter = last, self._inner_iter + k - 1
+            if self.optimizer is not None:         # what the text logger prints: the last iteration's
+                for group in self.optimizer.param_groups:
+                    group['lr'] = self.lr_at(last)
+            for h in list(self._hooks):            # priority order
+                if h in self._span_end or h in self._every or (h in self._interval and every_n_iters(self, h.interval)):
+                    fn = getattr(h, 'after_train_iter', None) or getattr(h, 'after_iter', None)
+                    if fn is not None:
+                        fn(self)
+            self._inner_iter += 1
+            self._iter += 1
+
+    def run(self, data_loaders, workflow, max_iters=None, **kwargs):
+        # (apis.train_nerf always hands the train and the val loader: a workflow of ('train', n) alone uses the first)
+        assert isinstance(data_loaders, list) and len(data_loaders) >= len(workflow)
+        workflow = [tuple(w) for w in workflow]
+        if max_iters is not None:
+            self._max_iters = max_iters
+        assert self._max_iters is not None, 'max_iters must be specified'
+        self.logger.info('workflow: %s, max: %d iters', workflow, self._max_iters)
+        self.call_hook('before_run')
+        self._classify()
+        self._make_engine()
+        iter_loaders = [x if isinstance(x, IterLoader) else IterLoader(x) for x in data_loaders]
+        self.call_hook('before_epoch')
+        while self.iter < self._max_iters:
+            for i, (mode, iters) in enumerate(workflow):
+                self._inner_iter = 0
+                if not isinstance(mode, str) or not hasattr(self, mode):
+                    raise ValueError('runner has no method named "{}" to run a workflow'.format(mode))
+                if mode == 'train':
+                    self.train_span(iter_loaders[i], iters)
+                else:
+                    for _ in range(iters):
+                        getattr(self, mode)(iter_loaders[i], **kwargs)
+        self.call_hook('after_epoch')
+        self.call_hook('after_run')
 
 
 RUNNERS = {c.__name__: c for c in (NerfTrainRunner, NerfTestRunner, KiloNerfTrainRunner, KiloNerfTestRunner, BungeeNerfTrainRunner,

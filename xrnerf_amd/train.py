@@ -224,8 +224,15 @@ class Trainer:
     backward -> [gradient all-reduce] -> fused Adam(+EMA)."""
 
     def __init__(self, device, n_img=20, H=800, W=800, seed=0, world_size=1, rank=0, dataset=None, ema=True, native_loop=True,
-                 fuse_adam=True, direct_step=True, march_window='side', prefetch_k6=True):
-        """The keyword switches (each overridable from the environment: XRNERF_TRAINER="fuse_adam=0,..."; xrnerf_amd/switches.py):
+                 fuse_adam=True, direct_step=True, march_window='side', prefetch_k6=True, net=None, optimizer=None, lr_at=None, log_window=None):
+        """What a config gives (xrnerf_amd.runner.NgpIterRunner; the defaults are this trainer's own, bit for bit what it built before they existed):
+        net             a built HashNerfNetwork, already on `device` (default: ngp_lego_model_cfg() built here, the global generator seeded with `seed`)
+        optimizer       a FusedAdam holding the three NGP tensors (default: lr 1e-2, betas (0.9, 0.99), eps 1e-15, weight decay 1e-6, EMA 0.05)
+        lr_at           iteration -> learning rate (default: step_lr(base_lr, .))
+        log_window      (float64 window tensor on `device`, slot_loss, slot_psnr) as runner.LogWindow.reserve hands it out, or None: every
+                        iteration's loss and psnr are added to the window on the device (ops.ngp_log_add; inside the native loop:
+                        xr_ngp_loop_run_logged), whichever path runs the iteration
+        The keyword switches (each overridable from the environment: XRNERF_TRAINER="fuse_adam=0,..."; xrnerf_amd/switches.py):
         native_loop     the iterations between two grid refreshes as native calls (xr_ngp_loop_run); False: one Python-driven step each
         fuse_adam       one GPU: the table scatter applies this optimiser's update itself (False: scatter, then the optimiser's launches)
         direct_step     one GPU: the fused step without an autograd graph (False: loss.backward() + optimizer.step())
@@ -239,15 +246,26 @@ class Trainer:
         opts.update(switches.trainer_overrides())
         if opts['march_window'] not in ('side', 'main', 'off'):
             raise ValueError("march_window is 'side', 'main' or 'off'")
-        torch.manual_seed(seed)                       # identical initial weights on every rank
         self.device = device
-        self.net = build_network(ngp_lego_model_cfg()).to(device)
+        if net is None:
+            torch.manual_seed(seed)                   # identical initial weights on every rank
+            net = build_network(ngp_lego_model_cfg()).to(device)
+        self.net = net
         self.data = dataset or SyntheticLego(device, n_img, H, W, seed=1, shuffle_seed=1 + rank)
         self.net.sampler.set_data(self.data.get_alldata(), self.data.get_info())     # PassDatasetHook
         self.net.sampler.on_sampled = self._on_sampled
         self.net.sampler.on_rewind = self._on_rewind
         self.net.sampler.on_refreshed = self._march_ahead
-        self.base_lr = 1e-2
+        self.base_lr = 1e-2 if optimizer is None else float(optimizer.param_groups[0].get('initial_lr', optimizer.param_groups[0]['lr']))
+        self.lr_at = lr_at if lr_at is not None else (lambda it: step_lr(self.base_lr, it))
+        if log_window is not None:
+            win, slot_loss, slot_psnr = log_window
+            if switches.step_mode() == 'modular':
+                raise ValueError('log_window: the log sums are taken from the fused step\'s loss scalars (XRNERF_STEP=modular has none)')
+            if world_size != 1 or win.dtype != torch.float64 or win.numel() != 2 * ops.LOG_WINDOW_SLOTS or win.device.type != torch.device(device).type:
+                raise ValueError('log_window: one GPU, a [%d] float64 window on %s' % (2 * ops.LOG_WINDOW_SLOTS, device))
+            log_window = (win, int(slot_loss), int(slot_psnr))
+        self.log_window = log_window
         self.iter = 0
         self.world_size, self.rank = world_size, rank
         self.dp_mode = os.environ.get('XRNERF_DP', 'allreduce')
@@ -261,8 +279,14 @@ class Trainer:
             table = self.net.mlp.embedder_pos.params
             shard = self.net.grad_sync.attach(table)
             opt_params = [shard] + [p for p in opt_params if p is not table]
-        self.opt = FusedAdam(opt_params, lr=self.base_lr, betas=(0.9, 0.99), eps=1e-15, weight_decay=1e-6,
-                             ema_momentum=0.05 if ema else None)
+        if optimizer is not None:
+            if world_size > 1:
+                raise ValueError('optimizer=: a given optimiser is the one-GPU form (data parallel builds its own over the shard)')
+            self.opt = optimizer
+            opt_params = [p for g in optimizer.param_groups for p in g['params']]
+        else:
+            self.opt = FusedAdam(opt_params, lr=self.base_lr, betas=(0.9, 0.99), eps=1e-15, weight_decay=1e-6,
+                                 ema_momentum=0.05 if ema else None)
         if world_size > 1 and self.dp_mode in ('allreduce', 'allreduce_bf16'):
             from . import dist as xdist                 # fused step: bucketed reduction under the table scatter
             self.net.grad_sync = xdist.BucketedGradSync(world_size, torch.bfloat16 if self.dp_mode == 'allreduce_bf16' else None)
@@ -402,7 +426,7 @@ class Trainer:
         net, data = self.net, self.data
         net.sampler.set_iter(self.iter)                                   # PassSamplerIterHook
         for g in self.opt.param_groups:
-            g['lr'] = step_lr(self.base_lr, self.iter)
+            g['lr'] = self.lr_at(self.iter)
         if self._queue and self._queue[0][0] < self.iter:
             net.sampler.rewind_marches()                                  # marched for iterations that are over
         batch = self._queue.pop(0)[1].batch() if (self._queue and self._queue[0][0] == self.iter) else None
@@ -428,6 +452,8 @@ class Trainer:
             out = net.train_step(batch, self.opt, lazy_log=self.lazy_log, direct=direct)
         finally:
             net._fuse_table_update = False
+        if self.log_window is not None:                                   # the same arithmetic as inside the native loop, behind the step
+            ops.ngp_log_add(net._last['loss_mse'], n_rays, *self.log_window)
         if out.get('grads_ready'):
             if not out['updates_applied']:
                 self.opt.step()
@@ -618,7 +644,7 @@ class _NativeLoop:
             key = key[:-2] + (dp(ops._workspaces.get((str(dev), 'mlpbwd'))), dp(ops._workspaces.get((str(dev), 'hgb'))))
             self._keep = (key, D, live_list, live_stats)
         # the schedules are this trainer's: lr per iteration, the EMA momentum of mmcv's EMAHook per update
-        lr = (C.c_float * k)(*[step_lr(tr.base_lr, tr.iter + j) for j in range(k)])
+        lr = (C.c_float * k)(*[tr.lr_at(tr.iter + j) for j in range(k)])
         mom = (C.c_float * k)(*[(FusedAdam._ema_momentum(g, int(S.adam_step) + 1 + j) if g['ema_momentum'] is not None else 0.0) for j in range(k)])
         stage, tev, tarr = None, None, None
         if ops.TIMER is not None:
@@ -635,7 +661,12 @@ class _NativeLoop:
         ops.mlp_range_tracking(dev, False)                # the iterations between two refreshes run the forward without its range count
         t_enq = time.perf_counter()
         try:
-            rc = L.xr_ngp_loop_run(C.byref(D), C.byref(S), k, n_rays, lr, mom, stage.encode() if stage else None, tarr, iarr)
+            if tr.log_window is not None:
+                win, slot_loss, slot_psnr = tr.log_window
+                rc = L.xr_ngp_loop_run_logged(C.byref(D), C.byref(S), k, n_rays, lr, mom, C.c_void_p(win.data_ptr()), slot_loss, slot_psnr,
+                                              stage.encode() if stage else None, tarr, iarr)
+            else:
+                rc = L.xr_ngp_loop_run(C.byref(D), C.byref(S), k, n_rays, lr, mom, stage.encode() if stage else None, tarr, iarr)
         finally:
             self.enqueue_s += time.perf_counter() - t_enq                # host time inside the native call (tools/hosttime2.py)
             ops.mlp_range_tracking(dev, True)
@@ -644,7 +675,7 @@ class _NativeLoop:
             if self.exchange is not None and self.exchange.error is not None:
                 err, self.exchange.error = self.exchange.error, None
                 raise err
-            _lib.check(rc, 'xr_ngp_loop_run')
+            _lib.check(rc, 'xr_ngp_loop_run_logged' if tr.log_window is not None else 'xr_ngp_loop_run')
         if stage is not None:
             ops.TIMER.events.setdefault(stage, []).extend((tev[2 * j], tev[2 * j + 1], 0) for j in range(k))
         sampler._pending_counts.extend(pf['host'] for pf in pfs)
